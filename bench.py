@@ -13,6 +13,13 @@ process per GPU); every rank assembles the S / g rows of its landmarks, rank 0
 gathers them over RCCL point-to-point, solves, and broadcasts the step; total
 work is fixed => strong scaling.
 
+A plain run sets up, warms up, times `--steps` steps and prints the line with
+the headline figure. `--full` adds everything else the line used to carry: the
+event-timed phase table and rooflines (a second run of the same steps), the
+drop-in end-to-end calls, the CPU baselines, and for the default workload the
+loop-closed GBA and config-2 LBA figures. `--dump-outputs DIR` writes what the
+timed steps left (the arrays a caller reads back) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -159,6 +166,30 @@ def reprojection_sse(p, q, t, X):
     return float(np.sum(e * e)), float(p.n_obs)
 
 
+DUMP_MAX_BYTES = 64 << 20  # bound of one --dump-outputs directory
+
+
+def dump_outputs(dirname: str, arrays: dict) -> None:
+    """--dump-outputs: write each array as DIRNAME/<name>.npy in float64
+    (float32 arrays stay float32, anything else becomes float32). When the
+    arrays together exceed DUMP_MAX_BYTES, the leading axis of the larger ones
+    is cut to a fixed seeded sample of rows (the same rows on every run)."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        arrs[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    budget = DUMP_MAX_BYTES // max(1, len(arrs))
+    if sum(a.nbytes for a in arrs.values()) > DUMP_MAX_BYTES:
+        rng = np.random.default_rng(0)
+        for name, a in arrs.items():
+            if a.nbytes > budget and a.ndim >= 1:
+                rows = max(1, budget // max(1, a.nbytes // len(a)))
+                arrs[name] = a[np.sort(rng.choice(len(a), size=rows, replace=False))]
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def host_cpu() -> dict:
     """CPU model and core counts of the host the baseline ran on (lscpu's
     model name from /proc/cpuinfo; nproc = the cores this process may use)."""
@@ -283,6 +314,8 @@ def bench_eg(args, world):
             t_tot += time.perf_counter() - t0
             n_it += n
         ms = 1000.0 * t_tot / max(1, n_it)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"sim3": ctx.eg_poses(), "chi2_end": np.array([st["chi2_end"]])})
     if world > 1:
         import torch
         tt = torch.tensor([ms], dtype=torch.float64)
@@ -306,7 +339,7 @@ def bench_eg(args, world):
                                     "whole LM iteration time; the solve is latency-bound (log2 p cyclic-reduction "
                                     "levels of 112-row block factorizations)"}}
         out["roofline"]["frac"] = out["roofline"]["achieved"] / MFMA_F64_PEAK_TFLOPS
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import oracle as O
             O.build()
             ref = O.OracleEG(pg)
@@ -383,6 +416,53 @@ def bench_matchers(ctx, ex, reps, cpu):
     return out
 
 
+def orb_extras(args, ctx, ex, img, reps, local_rank, world):
+    """The --full legs of bench_orb on the warmed-up extractor: the stereo pair
+    of extractors, the byte count behind k_orb_fast's roofline, the matchers."""
+    from sqrtlm.optimizer import Context
+    from sqrtlm.orb import ORBextractor
+    # a stereo Frame extracts left and right on two threads with two
+    # ORBextractor objects (Frame.cc stereo constructor): two contexts (own
+    # HIP stream each) driven concurrently, one overlapping the other's host
+    # quadtree and synchronisations
+    import threading
+    with Context(local_rank) as ctx2:
+        ex2 = ORBextractor(2000, 1.2, 8, 20, 7, ctx=ctx2)
+        ex2(img)
+        th = [threading.Thread(target=e.bench, args=(img, reps)) for e in (ex, ex2)]
+        t0 = time.perf_counter()
+        for t in th:
+            t.start()
+        for t in th:
+            t.join()
+        stereo_fps = 2 * reps / (time.perf_counter() - t0)
+    # algorithmic bytes of k_orb_fast per launch: every cell view it stages
+    # (overlapping 30-px cells + 6-px overlap) + 4 B per candidate + 4 B count
+    from oracle import orb as OB  # geometry only: the same cell loop as the reference
+    lw, lh, _, _ = OB.levels(OB.params(), 1241, 376)
+    view_bytes = 0
+    ncell = 0
+    for w, h in zip(lw.tolist(), lh.tolist()):
+        width, height = float(w - 32), float(h - 32)
+        nc, nr = int(width / 30), int(height / 30)
+        wc, hc = int(np.ceil(np.float32(width) / nc)), int(np.ceil(np.float32(height) / nr))
+        for i in range(nr):
+            y0 = 16 + i * hc
+            if y0 >= h - 16 - 3:
+                continue
+            for j in range(nc):
+                x0 = 16 + j * wc
+                if x0 >= w - 16 - 3:
+                    continue
+                view_bytes += (min(x0 + wc + 6, w - 16) - x0) * (min(y0 + hc + 6, h - 16) - y0)
+                ncell += 1
+    OB.build()
+    _k, _d, pyr = OB.extract(OB.params(), img, with_levels=True)
+    ncand = sum(len(OB.level_candidates(OB.params(), lev)) for lev in pyr)
+    matchers = bench_matchers(ctx, ex, reps=max(20, args.steps * 4), cpu=not args.no_cpu_baseline and world == 1)
+    return stereo_fps, view_bytes, ncell, ncand, matchers, OB
+
+
 def bench_orb(args, world):
     """ORB front end (SURVEY.md §8 f3): ORBextractor::operator() on a
     KITTI-00-size synthetic grey frame (1241x376, cfg/KITTI00-02.yaml: 2000
@@ -406,68 +486,35 @@ def bench_orb(args, world):
             dist.barrier()
         reps = max(50, args.steps * 10)
         ms, stages = ex.bench(img, reps)
-        # a stereo Frame extracts left and right on two threads with two
-        # ORBextractor objects (Frame.cc stereo constructor): two contexts (own
-        # HIP stream each) driven concurrently, one overlapping the other's host
-        # quadtree and synchronisations
-        import threading
-        with Context(local_rank) as ctx2:
-            ex2 = ORBextractor(2000, 1.2, 8, 20, 7, ctx=ctx2)
-            ex2(img)
-            th = [threading.Thread(target=e.bench, args=(img, reps)) for e in (ex, ex2)]
-            t0 = time.perf_counter()
-            for t in th:
-                t.start()
-            for t in th:
-                t.join()
-            stereo_fps = 2 * reps / (time.perf_counter() - t0)
-        # algorithmic bytes of k_orb_fast per launch: every cell view it stages
-        # (overlapping 30-px cells + 6-px overlap) + 4 B per candidate + 4 B count
-        from oracle import orb as OB  # geometry only: the same cell loop as the reference
-        lw, lh, _, _ = OB.levels(OB.params(), 1241, 376)
-        view_bytes = 0
-        ncell = 0
-        for w, h in zip(lw.tolist(), lh.tolist()):
-            width, height = float(w - 32), float(h - 32)
-            nc, nr = int(width / 30), int(height / 30)
-            wc, hc = int(np.ceil(np.float32(width) / nc)), int(np.ceil(np.float32(height) / nr))
-            for i in range(nr):
-                y0 = 16 + i * hc
-                if y0 >= h - 16 - 3:
-                    continue
-                for j in range(nc):
-                    x0 = 16 + j * wc
-                    if x0 >= w - 16 - 3:
-                        continue
-                    view_bytes += (min(x0 + wc + 6, w - 16) - x0) * (min(y0 + hc + 6, h - 16) - y0)
-                    ncell += 1
-        OB.build()
-        _k, _d, pyr = OB.extract(OB.params(), img, with_levels=True)
-        ncand = sum(len(OB.level_candidates(OB.params(), lev)) for lev in pyr)
-        matchers = bench_matchers(ctx, ex, reps=max(20, args.steps * 4), cpu=not args.no_cpu_baseline and world == 1)
+        if args.dump_outputs and rank == 0:
+            kd, dd = ex(img)  # what the timed call returns for this frame
+            dump_outputs(args.dump_outputs, dict({f: kd[f] for f in kd.dtype.names}, descriptors=dd))
+        extras = orb_extras(args, ctx, ex, img, reps, local_rank, world) if args.full else None
     if world > 1:
         import torch
         tt = torch.tensor([ms], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         ms = float(tt.item())
     if rank == 0:
-        alg = int(view_bytes) + 4 * int(ncand) + 4 * int(ncell)
-        t_fast = stages[1]
         out = {"metric": "frames/sec (ORB extraction, KITTI-00 frame)", "value": world * 1000.0 / ms,
                "unit": "frames/s", "n_gpus": world, "steps": reps, "warmup": args.warmup, "ms_per_step": ms,
                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
                "data": "synthetic grey frame (repo scene generator, seed 3)",
                "config": {"workload": "ORBextractor 1241x376, 2000 features, 8 levels", "keypoints": int(len(kps)),
                           "parallelism": f"replicas x{world}"},
-               "stage_ms": dict(zip(["pyramid", "fast", "compact", "blur", "describe", "host_quadtree"], stages)),
-               "stereo_two_extractors_frames_per_s": stereo_fps,
-               "matchers_ms_per_call": matchers,
-               "roofline": {"bound": "hbm", "kernel": "k_orb_fast", "algorithmic_bytes": alg,
-                            "achieved": alg / (t_fast * 1e-3) / 1e9 if t_fast > 0 else 0.0, "peak": HBM_PEAK_GBPS,
-                            "unit": "GB/s", "traffic": None, "launch_ms": t_fast,
-                            "note": "one launch per frame over all 30-px cells of all levels; latency-bound"}}
-        out["roofline"]["frac"] = out["roofline"]["achieved"] / HBM_PEAK_GBPS
-        if not args.no_cpu_baseline and world == 1:
+               "stage_ms": dict(zip(["pyramid", "fast", "compact", "blur", "describe", "host_quadtree"], stages))}
+        if extras is not None:
+            stereo_fps, view_bytes, ncell, ncand, matchers, OB = extras
+            alg = int(view_bytes) + 4 * int(ncand) + 4 * int(ncell)
+            t_fast = stages[1]
+            out["stereo_two_extractors_frames_per_s"] = stereo_fps
+            out["matchers_ms_per_call"] = matchers
+            out["roofline"] = {"bound": "hbm", "kernel": "k_orb_fast", "algorithmic_bytes": alg,
+                               "achieved": alg / (t_fast * 1e-3) / 1e9 if t_fast > 0 else 0.0, "peak": HBM_PEAK_GBPS,
+                               "unit": "GB/s", "traffic": None, "launch_ms": t_fast,
+                               "note": "one launch per frame over all 30-px cells of all levels; latency-bound"}
+            out["roofline"]["frac"] = out["roofline"]["achieved"] / HBM_PEAK_GBPS
+        if extras is not None and not args.no_cpu_baseline and world == 1:
             OB.build()
             p = OB.params()
             t0 = time.perf_counter()
@@ -527,9 +574,10 @@ def connect_rccl(ctx, rank, world, dist, make_uid):
     return f"rccl ({info['nranks']} ranks reported by ncclCommCount)", info["nranks"]
 
 
-def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=10.0):
+def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=10.0, dump=None):
     """One BA workload (config 4, the loop-closed config 4, or config 2) on this
-    rank's context; returns the bench dict on rank 0 (None elsewhere)."""
+    rank's context; returns the bench dict on rank 0 (None elsewhere). `dump`
+    names the directory the state after the timed steps is written to."""
     from sqrtlm.optimizer import Context
     from sqrtlm.shard import shard
     prob, desc = make_workload(config, args.scale)
@@ -545,15 +593,24 @@ def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=
         ctx.set_host_comm(rank, world, _gloo_allreduce, _gloo_p2p)
         comm_used, comm_ranks = "host (gloo, %d ranks on GPU 0)" % world, world
     ctx.set_problem(local)
-    # the timed run without the per-phase HIP events (they cost ≈2 %), then the
-    # same run from the same initial state with them, for the phase breakdown
-    # and the roofline's kernel times
+    # the timed run without the per-phase HIP events (they cost ≈2 %), then
+    # (--full) the same run from the same initial state with them, for the
+    # phase breakdown and the roofline's kernel times
     ms, _none, st = ctx.bench(args.warmup, args.steps, timers=False)
-    ctx.set_problem(local)
-    _ms_timed, kms, _st = ctx.bench(args.warmup, args.steps)
-    sse, nres = reprojection_sse(local, *ctx.poses(), ctx.points())
+    if dump:
+        # the state the timed steps left, as sqlm_get_poses / sqlm_get_points hand it
+        # to a caller; the cameras are replicated, the landmarks are this rank's shard
+        sfx = f"_rank{rank}" if world > 1 else ""
+        q_out, t_out = ctx.poses()
+        dump_outputs(dump, {"pose_q" + sfx: q_out, "pose_t" + sfx: t_out, "points" + sfx: ctx.points(),
+                            "chi2_end" + sfx: np.array([st["chi2_end"]])})
+    kms, sse, nres = {}, 0.0, 0.0
+    if args.full:
+        ctx.set_problem(local)
+        _ms_timed, kms, _st = ctx.bench(args.warmup, args.steps)
+        sse, nres = reprojection_sse(local, *ctx.poses(), ctx.points())
     e2e = None
-    if world == 1 and config == "lba":
+    if args.full and world == 1 and config == "lba":
         # the drop-in LocalBundleAdjustment call: host arrays in, the three-pass
         # schedule (5 Huber iterations, outlier tags, 10 more, + LiDAR 20), out
         reps = []
@@ -569,7 +626,7 @@ def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=
                "seconds_all": [r[0] for r in reps],
                "what": "sqlm_set_problem + sqlm_local_ba (3-pass schedule) + sqlm_get_poses/points, host buffers; "
                        "median of 3 calls by wall time"}
-    if world == 1 and config in ("gba", "gba_loop"):
+    if args.full and world == 1 and config in ("gba", "gba_loop"):
         # the drop-in call as the reference makes it (GlobalBundleAdjustemnt, 10
         # iterations): host arrays in, setup (sorting, tiles, H2D), the solve,
         # results out (D2H) — reported beside the metric, never as `value`
@@ -592,24 +649,12 @@ def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=
         tt = torch.tensor([ms], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         ms = float(tt.item())
+    if dist is not None and args.full:
         tt = torch.tensor([sse, nres], dtype=torch.float64)
         dist.all_reduce(tt)
         sse, nres = float(tt[0]), float(tt[1])
     out = None
     if rank == 0:
-        launches = max(1.0, st["trials"] / max(1, st["iterations"]))  # k_rcs_tile runs once per trial
-        t_rcs = kms["k_rcs_tile"] / launches
-        flops = algorithmic_flops_rcs(local)
-        ach_tf = flops / (t_rcs * 1e-3) / 1e12 if t_rcs > 0 else 0.0
-        traffic, tsrc = pmc_traffic("k_rcs_tile", config, local.n_obs) if world == 1 else (None, None)
-        # the landmark linearization runs inside k_landmark_update (speculative,
-        # DESIGN.md §2 step 7) unless SQLM_NO_SPEC=1 puts it back in k_linearize
-        spec = os.environ.get("SQLM_NO_SPEC", "0") in ("", "0")
-        lin_kernel = "k_landmark_update" if spec else "k_linearize"
-        t_lin = kms[lin_kernel] / (launches if spec else 1.0)
-        alg = algorithmic_bytes_update(local) if spec else algorithmic_bytes_linearize(local)
-        achieved = alg / (t_lin * 1e-3) / 1e9 if t_lin > 0 else 0.0
-        lin_traffic, _ = pmc_traffic(lin_kernel, config, local.n_obs) if world == 1 else (None, None)
         out = {
             "metric": "LM iterations/sec (synthetic KITTI-00-scale BA)",
             "value": 1000.0 / ms,
@@ -625,9 +670,25 @@ def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=
             "data": "synthetic (repo generator, SplitMix64 seed; inputs rounded through float32 like the reference)",
             "config": dict(desc, parallelism=f"landmark-shard x{world}", comm=comm_used, comm_ranks=comm_ranks),
             "trials_per_step": st["trials"] / max(1, st["iterations"]),
-            "final_rmse_px": None,
             "chi2_first": st["trace_chi2"][0] if st["trace_chi2"] else None,
             "chi2_last": st["chi2_end"],
+        }
+    if out is not None and args.full:
+        launches = max(1.0, st["trials"] / max(1, st["iterations"]))  # k_rcs_tile runs once per trial
+        t_rcs = kms["k_rcs_tile"] / launches
+        flops = algorithmic_flops_rcs(local)
+        ach_tf = flops / (t_rcs * 1e-3) / 1e12 if t_rcs > 0 else 0.0
+        traffic, tsrc = pmc_traffic("k_rcs_tile", config, local.n_obs) if world == 1 else (None, None)
+        # the landmark linearization runs inside k_landmark_update (speculative,
+        # DESIGN.md §2 step 7) unless SQLM_NO_SPEC=1 puts it back in k_linearize
+        spec = os.environ.get("SQLM_NO_SPEC", "0") in ("", "0")
+        lin_kernel = "k_landmark_update" if spec else "k_linearize"
+        t_lin = kms[lin_kernel] / (launches if spec else 1.0)
+        alg = algorithmic_bytes_update(local) if spec else algorithmic_bytes_linearize(local)
+        achieved = alg / (t_lin * 1e-3) / 1e9 if t_lin > 0 else 0.0
+        lin_traffic, _ = pmc_traffic(lin_kernel, config, local.n_obs) if world == 1 else (None, None)
+        out.update({
+            "final_rmse_px": float(np.sqrt(sse / max(1.0, nres))),
             "kernel_ms_per_step": kms,
             "kernel_timers": "a second run of the same steps from the same initial state with HIP events per phase "
                              "(ms_per_step and value come from the run without them)",
@@ -645,8 +706,7 @@ def run_ba(args, world, rank, local_rank, dist, config, cpu_iters=10, cpu_min_s=
                                    "traffic": lin_traffic, "algorithmic_bytes": alg, "launch_ms": t_lin,
                                    "survey_basis_GBps": survey_bytes_linearize(local) / (t_lin * 1e-3) / 1e9
                                    if t_lin and not spec else None},
-        }
-        out["final_rmse_px"] = float(np.sqrt(sse / max(1.0, nres)))
+        })
         if e2e is not None:
             out["end_to_end"] = e2e
         if not args.no_cpu_baseline and world == 1:
@@ -720,9 +780,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=["gba", "gba_loop", "lba", "eg", "orb"], default="gba")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink config 4 (parity / debugging only)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the timed steps: phase table and rooflines (a second run), end-to-end calls, CPU "
+                         "baselines, and for the default workload the loop-closed GBA and config-2 LBA figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed (poses, points, final chi2) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--no-extras", action="store_true",
-                    help="default line without the loop-closed GBA and config-2 LBA figures")
+                    help="--full line without the loop-closed GBA and config-2 LBA figures")
     ap.add_argument("--comm", choices=["rccl", "host"], default="rccl",
                     help="host = exchange through gloo on the host, all ranks on GPU 0 (1-GPU rehearsal of N>1)")
     args = ap.parse_args()
@@ -749,8 +814,9 @@ def main():
     if world > 1:
         import torch.distributed as dist  # rendezvous + scalar reductions only
         dist.init_process_group("gloo", init_method="env://")
-    out = run_ba(args, world, rank, local_rank, dist, args.config)
-    if out is not None and args.config == "gba" and world == 1 and not args.no_extras and args.scale == 1.0:
+    out = run_ba(args, world, rank, local_rank, dist, args.config, dump=args.dump_outputs)
+    if (out is not None and args.full and args.config == "gba" and world == 1 and not args.no_extras
+            and args.scale == 1.0):
         # the workloads the reference's own BA calls have, beside the metric's:
         # GBA only ever runs after a loop closure (LoopClosing.cc:877, :987-991),
         # and LocalMapping's local BA (LocalMapping.cc:131) is config 2's shape;

@@ -1,4 +1,4 @@
-"""A/B of library builds on the default bench (no CPU legs, no extras): value
+"""A/B of library builds on the default --full bench (no CPU legs, no extras): value
 and the event-timed phase table. usage: python scripts/ab_bench.py lib1.so lib2.so ...
 (AB_ARGS="--config lba" passes bench arguments; a lib written NAME.so:VAR=1
 runs NAME.so with that environment variable set)"""
@@ -15,7 +15,7 @@ for spec in sys.argv[1:]:
     for v in var:
         k, _, x = v.partition("=")
         env[k] = x
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-extras",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-extras",
                           "--steps", "20", "--warmup", "3"] + extra, env=env, capture_output=True, text=True,
                          check=True)
     d = json.loads(out.stdout.strip().splitlines()[-1])
