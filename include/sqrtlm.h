@@ -174,8 +174,27 @@ int sqlm_get_rcs_layout(sqlm_ctx *ctx, int out[8]);
  * invSigma2, Huber delta) were all float32 values and travelled as float4,
  * 0 if they took the double arrays; out[1] = reduced-camera solve: 0 none,
  * 1 cyclic reduction (per-level launches), 3 band + border, 4 dense
- * Cholesky (2 and 5 retired); out[2..7] = 0 (reserved). */
+ * Cholesky (2 and 5 retired); out[2] = kernel that forms the reduced camera
+ * system's partial sums: 0 none, 1 row fallback (launch_rcs: some landmark
+ * window wider than 24 free cameras), 2 k_rcs_tile mono, 3 k_rcs_tile stereo,
+ * 4 producer / consumer k_rcs_tile_p; out[3] = bitmask of the tile classes
+ * with at least one tile (bit NT, NT = ceil(6 cp / 16) accumulator tiles for
+ * a window of cp free cameras: 3, 4, 6, 8, 9); out[4] / out[5] = S blocks / g
+ * rows summed by a whole workgroup (more than 24 tile partials: n_long_s /
+ * n_long_g); out[6] = 1 if some landmark is observed twice by one camera
+ * (tile_dups); out[7] = longest track (tile_maxk). */
 int sqlm_get_exec_info(sqlm_ctx *ctx, int out[8]);
+
+/* The reduced camera system of the most recent LM trial the last optimize()
+ * launched (introspection for tests; no reference counterpart), in g2o's sign
+ * convention H dx = b with b = -J^T W r (block_solver.hpp:420-470): g
+ * [6 n_free] = b_p - sum_l H_pl (H_ll + lambda I)^-1 b_l, the Schur
+ * complement's right-hand side, and dx [6 n_free] = the camera step the trial
+ * applied as T <- exp(dx) T (zero if the solve met a non-positive pivot), both
+ * in free-camera (hessianIndex) order, tangent order [omega; upsilon].
+ * Synchronises the context stream. SQLM_ERR_STATE without a prepared problem,
+ * before any trial has run, or on a sharded context. */
+int sqlm_get_last_step(sqlm_ctx *ctx, double *g, double *dx);
 
 /* Converter::toSE3Quat / toCvMat(SE3Quat) (src/utils/Converter.cc:55-79,98-109):
  * float32 row-major 4x4 T_cw <-> (q, t). */

@@ -147,6 +147,7 @@ struct sqlm_ctx {
   // ---- host copy of the graph (caller order) ----
   bool has_problem = false;
   bool prepared = false;  // the last prepare() completed (CR plan, buffers valid)
+  bool step_valid = false;  // a trial has run since the last prepare() (d.g / d.dx hold its system)
   int n_pose = 0, n_pt = 0;
   int64_t n_obs = 0, n_lid = 0;
   std::vector<double> pose_q, pose_t, intr, pt;
@@ -925,6 +926,7 @@ int prepare(sqlm_ctx *c, int level) {
   // bring the previous call's errors home before the device copies change
   if (int s = fetch_errors(c)) return s;
   c->prepared = false;
+  c->step_valid = false;
   // the page-locked staging arrays are rewritten (or regrown) below: no DMA of
   // an earlier call, finished or abandoned on an error path, may still read them
   HIP_OK(hipStreamSynchronize(c->stream));
@@ -1614,7 +1616,7 @@ int prepare(sqlm_ctx *c, int level) {
   std::copy(tp.cls_cnt, tp.cls_cnt + kTileNtMax + 1, d.tile_cls_cnt);
   d.tile_dups = tp.dups ? 1 : 0;
   {
-    const char *tw = std::getenv("SQLM_TILE_PROD");  // read per setup: tests switch it
+    const char *tw = std::getenv("SQLM_TILE_PROD");  // read per setup: tests/test_gpu_first_trial.py switches it
     d.tile_prod = tw && std::atoi(tw) == 0 ? 0 : 1;
   }
   {
@@ -2073,6 +2075,7 @@ inline void hmark(sqlm_ctx *c, int i) {
 int trial_launch(sqlm_ctx *c, double lambda, bool &cam_after) {
   DevProblem &d = c->d;
   hmark(c, 0);  // since the previous trial's scalars arrived: the host's decision
+  c->step_valid = true;
   tmark(c, 2, false);
   launch_damp(d, lambda, c->stream);
   tmark(c, 2, true);
@@ -2706,6 +2709,30 @@ int sqlm_get_exec_info(sqlm_ctx *c, int out[8]) {
   for (int k = 0; k < 8; ++k) out[k] = 0;
   out[0] = c->d.obs_f32 ? 1 : 0;
   out[1] = c->d.nP == 0 ? 0 : !pl.enabled ? 4 : pl.R ? 3 : 1;
+  const DevProblem &d = c->d;
+  out[2] = d.nP == 0 ? 0 : !c->use_tiles ? 1 : rcs_tile_kernel(d);
+  if (c->use_tiles && d.n_tiles > 0)
+    for (int nt = 0; nt <= kTileNtMax; ++nt)
+      if (d.tile_cls_cnt[nt] > 0) out[3] |= 1 << nt;
+  out[4] = d.n_long_s;
+  out[5] = d.n_long_g;
+  out[6] = d.tile_dups;
+  out[7] = d.tile_maxk;
+  return SQLM_OK;
+}
+
+int sqlm_get_last_step(sqlm_ctx *c, double *g, double *dx) {
+  if (!c || !g || !dx) return SQLM_ERR_INVALID_ARG;
+  if (!c->has_problem || !c->prepared || !c->step_valid || c->comm.enabled()) return SQLM_ERR_STATE;
+  const size_t n = 6 * (size_t)c->d.nP;
+  if (n == 0) return SQLM_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  // g: rcs_put_g / k_rcs; dx: the dense solve's copy, or on a CR layout the
+  // pose update's copy of the CR / border solution. Nothing after the trial
+  // (speculative camera pass, finish) writes either.
+  HIP_OK(hipMemcpyAsync(g, c->d.g, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipMemcpyAsync(dx, c->d.dx, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_OK(hipStreamSynchronize(c->stream));
   return SQLM_OK;
 }
 

@@ -334,6 +334,9 @@ struct TileStreams {
 };
 void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k, hipStream_t st,
                       const TileStreams *ts = nullptr);
+// the kernel launch_rcs_tiles picks for d's tiles, in sqlm_get_exec_info's
+// numbering: 0 no tile, 2 k_rcs_tile mono, 3 k_rcs_tile stereo, 4 k_rcs_tile_p
+int rcs_tile_kernel(const DevProblem &d);
 void launch_rcs_reduce(const DevProblem &d, double lambda, hipStream_t st);
 #ifdef SQLM_TILE_PROF
 int tile_profile_read(long long *out);  // diagnostic build: k_rcs_tile phase counters

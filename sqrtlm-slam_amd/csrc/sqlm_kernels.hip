@@ -1783,9 +1783,9 @@ __global__ __launch_bounds__(kRedThreads) void k_rcs_reduce(DevProblem d, double
   }
 }
 
-// the producer / consumer kernel for classes up to 8 tiles wide (the
-// 9-wide class keeps k_rcs_tile: 15 accumulator tiles per consumer wave would
-// not fit its 3 waves per SIMD)
+// the producer / consumer kernel for every class up to SQLM_TILE_PROD_MAXNT
+// tiles wide (default 9: all of them; a lower value is an A/B switch that
+// keeps k_rcs_tile for the wider classes)
 #ifndef SQLM_TILE_PROD_MAXNT
 #define SQLM_TILE_PROD_MAXNT 9
 #endif
@@ -1795,6 +1795,15 @@ void launch_tile_p(int cnt, hipStream_t S, const DevProblem &d, double lambda, i
     hipLaunchKernelGGL((k_rcs_tile_p<NTT>), dim3(cnt), dim3(kTileThreads), 0, S, d, lambda, off);
   else
     hipLaunchKernelGGL((k_rcs_tile<NTT, false>), dim3(cnt), dim3(kTileThreads), 0, S, d, lambda, off);
+}
+
+int rcs_tile_kernel(const DevProblem &d) {
+  if (d.nP == 0 || d.n_tiles <= 0) return 0;
+  if (d.has_stereo) return 3;
+  // mono tiles without repeated cameras whose batches fit the producer wave:
+  // the producer / consumer kernel
+  const bool prod_tiles = !d.tile_dups && d.tile_maxk * kTileBL <= kProdObs && d.tile_prod;
+  return prod_tiles ? 4 : 2;
 }
 
 void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k, hipStream_t st,
@@ -1831,9 +1840,7 @@ void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k,
       (void)hipEventRecord(ts->fork, st);
       TH_MARK;
     }
-    // mono tiles without repeated cameras whose batches fit the producer wave:
-    // the producer / consumer kernel
-    const bool prod_tiles = !d.has_stereo && !d.tile_dups && d.tile_maxk * kTileBL <= kProdObs && d.tile_prod;
+    const bool prod_tiles = rcs_tile_kernel(d) == 4;
 #define SQLM_TILE(NTT, S)                                                                                     \
   do {                                                                                                        \
     const int cnt = d.tile_cls_cnt[NTT], off = d.tile_cls_off[NTT];                                            \

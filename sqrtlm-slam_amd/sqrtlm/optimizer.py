@@ -109,7 +109,19 @@ class Context:
         out = (C.c_int * 8)()
         check(lib().sqlm_get_exec_info(self._h, out), "sqlm_get_exec_info")
         solve = {0: "none", 1: "cr_levels", 3: "band+border", 4: "dense"}[out[1]]
-        return dict(obs_f32=bool(out[0]), solve=solve)
+        tile_kernel = {0: "none", 1: "rows", 2: "tile_mono", 3: "tile_stereo", 4: "tile_producer"}[out[2]]
+        return dict(obs_f32=bool(out[0]), solve=solve, tile_kernel=tile_kernel, tile_kernel_id=out[2],
+                    tile_classes={nt for nt in range(32) if out[3] >> nt & 1}, n_long_s=out[4], n_long_g=out[5],
+                    tile_dups=out[6], tile_maxk=out[7])
+
+    def last_step(self):
+        """(g, dx) of the most recent LM trial (sqlm_get_last_step): the reduced
+        camera system's right-hand side and the camera step, each (n_free, 6) in
+        free-camera order, g2o's sign convention (H dx = b, b = -J^T W r)."""
+        n = self.rcs_layout()["n_free"]
+        g, dx = np.zeros((n, 6)), np.zeros((n, 6))
+        check(lib().sqlm_get_last_step(self._h, ptr(g), ptr(dx)), "sqlm_get_last_step")
+        return g, dx
 
     def bench(self, warmup: int, n: int, timers: bool = True):
         """(ms per LM iteration, per-phase ms from HIP events or {} without

@@ -55,6 +55,8 @@ def test_null_and_invalid_arguments():
     assert L.sqlm_set_problem(None, 0, None, None, None, None, 0, None, C.c_int64(0), None, None, None, None, None,
                               None) == -1
     assert L.sqlm_optimize(None, 0, 1, C.c_double(0), None, None, None) == -1
+    buf = (C.c_double * 6)()
+    assert L.sqlm_get_last_step(None, buf, buf) == -1
 
 
 def test_converter_matches_oracle(oracle):
