@@ -148,6 +148,22 @@ int sqlm_eg_get_edge_chi2(sqlm_ctx *ctx, double *chi2);
  * k_eg_linearize: J [n_edge][2][7][7] row-major, [e][0] = d e / d S_i,
  * [e][1] = d e / d S_j, zero for a fixed vertex. Diagnostics / parity tests. */
 int sqlm_eg_get_jacobians(sqlm_ctx *ctx, double *J);
+/* The linear system of the most recent LM trial of the last sqlm_eg_optimize
+ * (introspection for tests; no reference counterpart), in g2o's sign
+ * convention (H + lambda I) dx = b with b = -J^T Omega e: the right-hand side
+ * b [7 n_free] and the solution dx [7 n_free] the trial applied as
+ * S <- Sim3(dx) S, both in free-vertex (hessianIndex, i.e. id) order whatever
+ * layout the solver chose. SQLM_ERR_STATE before any trial has run. */
+int sqlm_eg_get_last_step(sqlm_ctx *ctx, double *b, double *dx);
+/* What the last sqlm_eg_optimize ran: out[0] = solve path, 1 band by cyclic
+ * reduction + border complement, 2 arrow Cholesky, 3 dense Cholesky; out[1] =
+ * n_free; out[2] = 112-row band blocks p (0 on the dense layout); out[3] =
+ * border vertices; out[4] = nc, the padded order of the border complement,
+ * out[5] = R, the padded count of cyclic-reduction right-hand sides, out[6] =
+ * n_last, the rows factored in the complement's last block (all 0 off path
+ * 1, n_last 0 without a border); out[7] = 1 if an information matrix was
+ * given. SQLM_ERR_STATE before any optimize with a free vertex. */
+int sqlm_eg_get_exec_info(sqlm_ctx *ctx, int out[8]);
 
 /* Results (write-back inputs, g2oOptimizer.cc:1167-1189, :306-360). */
 int sqlm_get_poses(sqlm_ctx *ctx, double *pose_q, double *pose_t);

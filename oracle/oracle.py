@@ -286,6 +286,15 @@ def sim3_mul(a, b):
     return o
 
 
+def sim3_oplus(S, u, fix_scale=0):
+    """VertexSim3Expmap::oplusImpl as eg_ref.c applies it: Sim3(u) * S, the
+    scale component of u zeroed first when the scale is fixed."""
+    u = np.array(u, np.float64)
+    if fix_scale:
+        u[6] = 0.0
+    return sim3_mul(sim3_from_update(u), S)
+
+
 def sim3_inverse(a):
     o = np.zeros(8)
     lib().orc_sim3_inverse(_f(a), _p(o))

@@ -2650,6 +2650,18 @@ int sqlm_eg_get_jacobians(sqlm_ctx *c, double *J) {
   return eg_get_jacobians(c->eg, J);
 }
 
+int sqlm_eg_get_last_step(sqlm_ctx *c, double *b, double *dx) {
+  if (!c || !b || !dx) return SQLM_ERR_INVALID_ARG;
+  if (!c->eg) return SQLM_ERR_STATE;
+  return eg_get_last_step(c->eg, b, dx);
+}
+
+int sqlm_eg_get_exec_info(sqlm_ctx *c, int out[8]) {
+  if (!c || !out) return SQLM_ERR_INVALID_ARG;
+  if (!c->eg) return SQLM_ERR_STATE;
+  return eg_get_exec_info(c->eg, out);
+}
+
 int sqlm_global_ba(sqlm_ctx *c, int iterations, const volatile uint8_t *stop, sqlm_stats *st, int *n_iter) {
   return sqlm_optimize(c, 0, iterations, 0.0, stop, st, n_iter);
 }

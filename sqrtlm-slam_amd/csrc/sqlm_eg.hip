@@ -440,6 +440,10 @@ struct EGSolver {
   std::vector<int32_t> ei, ej;
   std::vector<void *> mem;
   double *h_scal = nullptr;
+  // introspection of the last optimize() (sqlm_eg_get_exec_info / sqlm_eg_get_last_step)
+  bool info_valid = false, step_valid = false;
+  int exec_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::vector<double> last_b, last_x;  // [7 n_free], free-vertex (hessianIndex) order
 
   ~EGSolver() { release(); if (h_scal) (void)hipHostFree(h_scal); }
   void release() {
@@ -474,6 +478,7 @@ int EGSolver::optimize(int iterations, double user_lambda, const volatile uint8_
   if (!stt) stt = &local;
   std::memset(stt, 0, sizeof(*stt));
   if (n_iter) *n_iter = -1;
+  info_valid = step_valid = false;
   // initializeOptimization: active edges (not all-fixed), active vertices, free hidx in id order
   std::vector<int> act, hid(nK, -1);
   std::vector<uint8_t> vact(nK, 0);
@@ -486,6 +491,9 @@ int EGSolver::optimize(int iterations, double user_lambda, const volatile uint8_
   for (int p = 0; p < nK; ++p)
     if (vact[p] && !fixed[p]) hid[p] = nP++;
   if (nP == 0) return SQLM_OK;  // "0 vertices to optimize": optimize() returns -1
+  std::vector<int> free_vtx;  // hessianIndex -> vertex id
+  for (int p = 0; p < nK; ++p)
+    if (hid[p] >= 0) free_vtx.push_back(p);
   const int64_t A_ = (int64_t)act.size();
   const int n = 7 * nP;
   // Block-arrow layout: g2o's id order keeps the essential graph banded except
@@ -648,6 +656,13 @@ int EGSolver::optimize(int iterations, double user_lambda, const volatile uint8_
   d.act = d_act; d.ei = d_ei; d.ej = d_ej; d.hid = d_hid; d.C = d_C; d.info = d_info;
   d.dst = d_dst; d.src_ptr = d_sptr; d.src = d_src;
   if (hipMemsetAsync(d.b, 0, sizeof(double) * n_pad, st) != hipSuccess) return SQLM_ERR_HIP;
+  {
+    const int n_last = use_cr && c.nb > 0 ? ((c.nb - (c.nc - kCRMaxN)) + 15) / 16 * 16 : 0;
+    const int ei8[8] = {use_cr ? 1 : arrow ? 2 : 3, nP, band_blk, nborder, use_cr ? c.nc : 0, use_cr ? c.R : 0,
+                        n_last, info.empty() ? 0 : 1};
+    std::memcpy(exec_info, ei8, sizeof(ei8));
+    info_valid = true;
+  }
   const int nD = (int)dst.size();
   const int eb = (int)((A_ + kEGBlock - 1) / kEGBlock), sb = (n_pad + kEGBlock - 1) / kEGBlock;
   auto fetch = [&]() -> int {
@@ -750,10 +765,25 @@ int EGSolver::optimize(int iterations, double user_lambda, const volatile uint8_
   if (n_iter) *n_iter = its;
   // results: estimates and the last computed (g2o: possibly rejected-trial) errors
   std::vector<double> aerr(7 * A_);
+  // and, once a trial has run, its right-hand side and solution in the slot layout
+  std::vector<double> hb(stt->trials > 0 ? n_pad : 0), hx(hb.size());
   if (hipMemcpyAsync(S.data(), Sd[0], S.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(aerr.data(), d.err, aerr.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (!hb.empty() &&
+       (hipMemcpyAsync(hb.data(), d.b, hb.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(hx.data(), x, hx.size() * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess)) ||
       hipStreamSynchronize(st) != hipSuccess)
     return SQLM_ERR_HIP;
+  if (!hb.empty()) {  // slot permutation undone, padding rows dropped
+    last_b.resize(7 * (size_t)nP);
+    last_x.resize(7 * (size_t)nP);
+    for (int h = 0; h < nP; ++h) {
+      const int slot = hid[free_vtx[h]];
+      std::memcpy(&last_b[7 * (size_t)h], &hb[7 * (size_t)slot], 7 * sizeof(double));
+      std::memcpy(&last_x[7 * (size_t)h], &hx[7 * (size_t)slot], 7 * sizeof(double));
+    }
+    step_valid = true;
+  }
   for (int64_t k = 0; k < A_; ++k) std::memcpy(&err[7 * (size_t)act[k]], &aerr[7 * k], 7 * sizeof(double));
   release();
   return SQLM_OK;
@@ -785,6 +815,7 @@ int eg_set_problem(EGSolver *s, int n_kf, const double *Siw, const uint8_t *fixe
   if (info) s->info.assign(info, info + 49 * (size_t)n_edge);
   else s->info.clear();
   s->err.assign(7 * (size_t)n_edge, 0.0);
+  s->info_valid = s->step_valid = false;
   return SQLM_OK;
 }
 
@@ -837,6 +868,21 @@ int eg_get_edge_chi2(const EGSolver *s, double *chi2) {
     }
     chi2[e] = c;
   }
+  return SQLM_OK;
+}
+
+int eg_get_last_step(const EGSolver *s, double *b, double *dx) {
+  if (!b || !dx) return SQLM_ERR_INVALID_ARG;
+  if (!s->step_valid) return SQLM_ERR_STATE;
+  std::memcpy(b, s->last_b.data(), s->last_b.size() * sizeof(double));
+  std::memcpy(dx, s->last_x.data(), s->last_x.size() * sizeof(double));
+  return SQLM_OK;
+}
+
+int eg_get_exec_info(const EGSolver *s, int out[8]) {
+  if (!out) return SQLM_ERR_INVALID_ARG;
+  if (!s->info_valid) return SQLM_ERR_STATE;
+  std::memcpy(out, s->exec_info, sizeof(s->exec_info));
   return SQLM_OK;
 }
 

@@ -409,6 +409,8 @@ int eg_optimize(EGSolver *s, int iterations, double user_lambda, const volatile 
 int eg_get_poses(const EGSolver *s, double *Siw);
 int eg_get_edge_chi2(const EGSolver *s, double *chi2);
 int eg_get_jacobians(EGSolver *s, double *J);
+int eg_get_last_step(const EGSolver *s, double *b, double *dx);
+int eg_get_exec_info(const EGSolver *s, int out[8]);
 
 // ORB front end (sqlm_orb.hip): one engine per context, on the context's stream.
 struct OrbEngine;

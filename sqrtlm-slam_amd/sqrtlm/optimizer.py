@@ -250,6 +250,23 @@ class Context:
         check(lib().sqlm_eg_get_jacobians(self._h, ptr(out)), "sqlm_eg_get_jacobians")
         return out
 
+    def eg_exec_info(self) -> dict:
+        """What the last eg_optimize() ran (sqlm_eg_get_exec_info)."""
+        out = (C.c_int * 8)()
+        check(lib().sqlm_eg_get_exec_info(self._h, out), "sqlm_eg_get_exec_info")
+        solve = {1: "cr", 2: "arrow_cholesky", 3: "dense"}[out[0]]
+        return dict(solve=solve, n_free=out[1], p=out[2], border=out[3], nc=out[4], R=out[5], n_last=out[6],
+                    info=bool(out[7]))
+
+    def eg_last_step(self):
+        """(b, dx) of the most recent LM trial of the last eg_optimize()
+        (sqlm_eg_get_last_step): right-hand side and solution of
+        (H + lambda I) dx = b, each (n_free, 7) in free-vertex (id) order."""
+        n = self.eg_exec_info()["n_free"]
+        b, dx = np.zeros((n, 7)), np.zeros((n, 7))
+        check(lib().sqlm_eg_get_last_step(self._h, ptr(b), ptr(dx)), "sqlm_eg_get_last_step")
+        return b, dx
+
 
 def comm_unique_id() -> bytes:
     n = lib().sqlm_comm_id_size()
