@@ -2,8 +2,8 @@
 //
 // Drop-in sibling of g2oOptimizer (src/backend/g2oOptimizer.cc) for the
 // calls the MI355X backend implements: LocalBundleAdjustment,
-// BundleAdjustment, GlobalBundleAdjustemnt and OptimizeEssentialGraph
-// (include/backend/Optimizer.h:50-65).
+// BundleAdjustment, GlobalBundleAdjustemnt, OptimizeEssentialGraph and
+// OptimizeSim3 (include/backend/Optimizer.h:50-69).
 // It is meant to be added to the reference tree as include/backend/hipOptimizer.h
 // + src/backend/hipOptimizer.cc and selected in Optimizer.cc's dispatch
 // (see INTEGRATION.md §4); it builds against the reference's own headers and
@@ -51,6 +51,11 @@ class hipOptimizer {
                                      const LoopClosing::KeyFrameAndPose& CorrectedSim3,
                                      const std::map<KeyFrame*, std::set<KeyFrame*> >& LoopConnections,
                                      const bool& bFixScale);
+  // g2oOptimizer::OptimizeSim3 (g2oOptimizer.cc:1560-1793) on the GPU
+  // (sqlm_sim3_optimize, adapter/hipOptimizerSim3.cc): returns the inlier
+  // count, updates g2oS12 and clears the rejected entries of vpMatches1.
+  static int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1,
+                          g2o::Sim3& g2oS12, const float th2, const bool bFixScale);
 
   // Capture mode around the g2o backend (Optimizer.cc dispatch): Begin*
   // records the seam inputs, End* the g2o write-back, then the file is written.

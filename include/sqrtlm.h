@@ -165,6 +165,57 @@ int sqlm_eg_get_last_step(sqlm_ctx *ctx, double *b, double *dx);
  * given. SQLM_ERR_STATE before any optimize with a free vertex. */
 int sqlm_eg_get_exec_info(sqlm_ctx *ctx, int out[8]);
 
+/* Sim3 alignment of a loop candidate: g2oOptimizer::OptimizeSim3
+ * (g2oOptimizer.cc:1560-1793), n_prob independent problems in one call (the
+ * reference's call is n_prob = 1). One free VertexSim3Expmap S12 per problem
+ * and, per surviving correspondence ("pair"), an EdgeSim3ProjectXYZ
+ * e12 = obs1 - cam_map1(project(S12.map(X2c))) and an EdgeInverseSim3ProjectXYZ
+ * e21 = obs2 - cam_map2(project(S12^-1.map(X1c))) (types_seven_dof_expmap.h:
+ * 130-171), information info * I2, Huber delta (float)sqrt(th2), numeric
+ * Jacobians (central differences through oplus, delta 1e-9). Schedule: stage 1
+ * optimize(iters[0]); pairs with chi2 > th2 on either edge are removed
+ * (pair_state 1, n_bad of them); fewer than 10 left: n_inliers = 0 and S12_out
+ * = S12; otherwise a fresh initializeOptimization and optimize(n_bad > 0 ?
+ * iters[1] : iters[2]); pairs failing the same check get pair_state 2, the
+ * others (state 0) are counted in n_inliers. The two checks read the plain
+ * chi2 of the last computed error (it may belong to a rejected trial).
+ * The whole schedule of every problem runs in one kernel launch. */
+#define SQLM_SIM3_TRACE_MAX 16
+typedef struct sqlm_sim3_stats {
+  int n_corr, n_bad;
+  int iterations[2], trials[2], result[2]; /* per stage, as in sqlm_stats */
+  double chi2_begin[2], chi2_end[2], lambda_end[2];
+  int trace_len[2];
+  double trace_chi2[2][SQLM_SIM3_TRACE_MAX];
+  double trace_lambda[2][SQLM_SIM3_TRACE_MAX];
+  int trace_trials[2][SQLM_SIM3_TRACE_MAX];
+} sqlm_sim3_stats;
+int sqlm_sim3_optimize(sqlm_ctx *ctx, int n_prob,
+    const double *S12,            /* [n_prob][8] qx qy qz qw tx ty tz s, the ABI's Sim3 layout        */
+    const double *intr1, const double *intr2,   /* [n_prob][4] fx fy cx cy of KF1 / KF2              */
+    const uint8_t *fix_scale, const double *th2,/* [n_prob]                                            */
+    const int64_t *pair_off,      /* [n_prob+1] CSR offsets into the pair arrays                       */
+    const double *X1c, const double *X2c,       /* [n_pair][3] pMP1 in camera 1, pMP2 in camera 2    */
+    const double *obs1, const double *obs2,     /* [n_pair][2] kpUn1.pt, kpUn2.pt                     */
+    const double *info1, const double *info2,   /* [n_pair] invSigma2 of each keypoint's octave       */
+    const int32_t iters[3],       /* NULL = {5, 10, 5}: stage 1, stage 2 if nBad>0, stage 2 otherwise  */
+    double user_lambda,           /* 0 = g2o's computeLambdaInit (the reference); >0 for tests         */
+    double *S12_out, int32_t *n_inliers, uint8_t *pair_state, sqlm_sim3_stats *stats);
+/* Introspection of the last sqlm_sim3_optimize of the context (tests; no
+ * reference counterpart); SQLM_ERR_STATE before any call.
+ * chi2 [n_pair][2 checks][2 edges]: the e->chi2() values the check after
+ * stage 1 and the final check read (e12, e21); a pair removed after stage 1
+ * keeps its stage-1 values in check 1.
+ * e [n_pair][2][2], J [n_pair][2][2][7]: error and numeric Jacobian of e12 and
+ * e21 at the input S12.
+ * The last LM trial of problem `prob`, in g2o's convention (H + lambda I) dx
+ * = b with b = -J^T rho' Omega e: H [49] row-major (undamped), b [7], dx [7]
+ * (zero if the damped system met a non-positive pivot); SQLM_ERR_STATE if the
+ * problem ran no trial. */
+int sqlm_sim3_get_pair_chi2(sqlm_ctx *ctx, double *chi2);
+int sqlm_sim3_get_linearization(sqlm_ctx *ctx, double *e, double *J);
+int sqlm_sim3_get_last_step(sqlm_ctx *ctx, int prob, double *H, double *b, double *dx);
+
 /* Results (write-back inputs, g2oOptimizer.cc:1167-1189, :306-360). */
 int sqlm_get_poses(sqlm_ctx *ctx, double *pose_q, double *pose_t);
 int sqlm_get_points(sqlm_ctx *ctx, double *pt);

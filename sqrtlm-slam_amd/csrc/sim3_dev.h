@@ -206,6 +206,20 @@ SQLM_HD void eg_edge_error(const double Si[8], const double Sj[8], const double 
   sim3_log(b, e);
 }
 
+// EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ error (types_seven_dof_expmap.h
+// :130-171) for the Sim3 given (S12, or its inverse for the inverse edge):
+// obs - cam_map(project(S.map(X))), map = s * (r * x) + t (sim3.h:144-146),
+// K = fx fy cx cy
+SQLM_HD void sim3_project_error(const double S[8], const double X[3], const double K[4], const double obs[2],
+                                double e[2]) {
+  double r[3];
+  q_rotate(S, X, r);
+  const double p0 = S[7] * r[0] + S[4], p1 = S[7] * r[1] + S[5], p2 = S[7] * r[2] + S[6];
+  const double u = p0 / p2, v = p1 / p2;
+  e[0] = obs[0] - (u * K[0] + K[2]);
+  e[1] = obs[1] - (v * K[1] + K[3]);
+}
+
 #pragma clang fp contract(on)
 
 }  // namespace sqlm

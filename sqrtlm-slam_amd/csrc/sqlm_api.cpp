@@ -213,6 +213,7 @@ struct sqlm_ctx {
   GatherTab gather;
   bool need_maxdiag = false;
   EGSolver *eg = nullptr;
+  Sim3Solver *sim3 = nullptr;
   OrbEngine *orb = nullptr;
   // ---- timing ----
   hipEvent_t ev[2 * SQLM_NKERNEL_TIMERS] = {};
@@ -2444,6 +2445,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   (void)hipStreamSynchronize(c->stream);
   comm_destroy(c->comm);
   if (c->eg) eg_destroy(c->eg);
+  if (c->sim3) sim3_destroy(c->sim3);
   if (c->orb) orb_destroy(c->orb);
   for (auto &b : c->bufs)
     if (b.p) (void)hipFree(b.p);
@@ -2660,6 +2662,44 @@ int sqlm_eg_get_exec_info(sqlm_ctx *c, int out[8]) {
   if (!c || !out) return SQLM_ERR_INVALID_ARG;
   if (!c->eg) return SQLM_ERR_STATE;
   return eg_get_exec_info(c->eg, out);
+}
+
+int sqlm_sim3_optimize(sqlm_ctx *c, int n_prob, const double *S12, const double *intr1, const double *intr2,
+                       const uint8_t *fix_scale, const double *th2, const int64_t *pair_off, const double *X1c,
+                       const double *X2c, const double *obs1, const double *obs2, const double *info1,
+                       const double *info2, const int32_t iters[3], double user_lambda, double *S12_out,
+                       int32_t *n_inliers, uint8_t *pair_state, sqlm_sim3_stats *stats) {
+  if (!c || n_prob < 0 || !pair_off) return SQLM_ERR_INVALID_ARG;
+  if (iters && (iters[0] < 0 || iters[1] < 0 || iters[2] < 0)) return SQLM_ERR_INVALID_ARG;
+  if (n_prob > 0 && (!S12 || !intr1 || !intr2 || !fix_scale || !th2 || !S12_out || !n_inliers))
+    return SQLM_ERR_INVALID_ARG;
+  for (int k = 0; k < n_prob; ++k)
+    if (pair_off[k + 1] < pair_off[k] || pair_off[k + 1] - pair_off[k] > INT32_MAX) return SQLM_ERR_INVALID_ARG;
+  if (pair_off[0] < 0) return SQLM_ERR_INVALID_ARG;
+  if (pair_off[n_prob] > pair_off[0] && (!X1c || !X2c || !obs1 || !obs2 || !info1 || !info2 || !pair_state))
+    return SQLM_ERR_INVALID_ARG;
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  if (!c->sim3 && !(c->sim3 = sim3_create(c->stream))) return SQLM_ERR_OOM;
+  return sim3_optimize(c->sim3, n_prob, S12, intr1, intr2, fix_scale, th2, pair_off, X1c, X2c, obs1, obs2, info1, info2,
+                       iters, user_lambda, S12_out, n_inliers, pair_state, stats);
+}
+
+int sqlm_sim3_get_pair_chi2(sqlm_ctx *c, double *chi2) {
+  if (!c || !chi2) return SQLM_ERR_INVALID_ARG;
+  if (!c->sim3) return SQLM_ERR_STATE;
+  return sim3_get_pair_chi2(c->sim3, chi2);
+}
+
+int sqlm_sim3_get_linearization(sqlm_ctx *c, double *e, double *J) {
+  if (!c || (!e && !J)) return SQLM_ERR_INVALID_ARG;
+  if (!c->sim3) return SQLM_ERR_STATE;
+  return sim3_get_linearization(c->sim3, e, J);
+}
+
+int sqlm_sim3_get_last_step(sqlm_ctx *c, int prob, double *H, double *b, double *dx) {
+  if (!c || !H || !b || !dx) return SQLM_ERR_INVALID_ARG;
+  if (!c->sim3) return SQLM_ERR_STATE;
+  return sim3_get_last_step(c->sim3, prob, H, b, dx);
 }
 
 int sqlm_global_ba(sqlm_ctx *c, int iterations, const volatile uint8_t *stop, sqlm_stats *st, int *n_iter) {

@@ -40,8 +40,9 @@ struct LMCtl {
 // levenberg.cpp:110-160 (rho, lambda update, accept) and the iteration end of
 // sparse_optimizer.cpp:376-414 with levenberg.cpp:150-163 (Terminate on
 // qmax == 10 or rho == 0, Raul's criterion). Returns true if the trial state
-// is accepted (the caller swaps the state buffers).
-inline bool lm_decide(LMCtl &c, double chi_cur, double chi_new, double scale, bool ok, bool stop) {
+// is accepted (the caller swaps the state buffers). Host and device: the
+// batched Sim3 alignment (sqlm_sim3.hip) runs its LM loop inside the kernel.
+__host__ __device__ inline bool lm_decide(LMCtl &c, double chi_cur, double chi_new, double scale, bool ok, bool stop) {
   if (c.qmax == 0 && c.its > 0) {  // a fresh linearization's computeActiveErrors
     c.currentChi = chi_cur;
     c.iniChi = chi_cur;
@@ -59,7 +60,12 @@ inline bool lm_decide(LMCtl &c, double chi_cur, double chi_new, double scale, bo
   rho /= scl;
   bool acc = false;
   if (rho > 0 && std::isfinite(tempChi)) {
+#ifdef __HIP_DEVICE_COMPILE__
+    const double r3 = 2 * rho - 1;
+    double alpha = 1. - r3 * r3 * r3;
+#else
     double alpha = 1. - std::pow(2 * rho - 1, 3);  // levenberg.cpp:136, the same libm call
+#endif
     alpha = (2. / 3. < alpha) ? 2. / 3. : alpha;         // std::min(alpha, 2/3)
     const double sf = (1. / 3. < alpha) ? alpha : 1. / 3.;  // std::max(1/3, alpha)
     c.lambda *= sf;
@@ -411,6 +417,37 @@ int eg_get_edge_chi2(const EGSolver *s, double *chi2);
 int eg_get_jacobians(EGSolver *s, double *J);
 int eg_get_last_step(const EGSolver *s, double *b, double *dx);
 int eg_get_exec_info(const EGSolver *s, int out[8]);
+
+// Batched Sim3 alignment (sqlm_sim3.cpp host, sqlm_sim3.hip kernel): one
+// solver per context, on the context's stream; its buffers are reused.
+struct Sim3Dev {  // device pointers of one sqlm_sim3_optimize call
+  int n_prob = 0;
+  int iters[3] = {5, 10, 5};
+  double user_lambda = 0.0;
+  const double *S12 = nullptr, *intr1 = nullptr, *intr2 = nullptr, *th2 = nullptr;  // [n_prob][8|4|4|1]
+  const uint8_t *fix_scale = nullptr;                                               // [n_prob]
+  const int64_t *pair_off = nullptr;                                                // [n_prob+1]
+  const double *X1c = nullptr, *X2c = nullptr, *obs1 = nullptr, *obs2 = nullptr, *info1 = nullptr, *info2 = nullptr;
+  double *S12_out = nullptr;               // [n_prob][8]
+  int32_t *n_inliers = nullptr;            // [n_prob]
+  uint8_t *pair_state = nullptr;           // [n_pair]
+  struct sqlm_sim3_stats *stats = nullptr; // [n_prob]
+  double *pair_chi2 = nullptr;             // [n_pair][2 checks][2 edges]
+  double *lin_e = nullptr, *lin_J = nullptr;  // [n_pair][2][2], [n_pair][2][2][7]
+  double *last_step = nullptr;             // [n_prob][64]: H 49, b 7, dx 7, valid
+};
+void launch_sim3(const Sim3Dev &d, hipStream_t st);
+struct Sim3Solver;
+Sim3Solver *sim3_create(hipStream_t st);
+void sim3_destroy(Sim3Solver *s);
+int sim3_optimize(Sim3Solver *s, int n_prob, const double *S12, const double *intr1, const double *intr2,
+                  const uint8_t *fix_scale, const double *th2, const int64_t *pair_off, const double *X1c,
+                  const double *X2c, const double *obs1, const double *obs2, const double *info1, const double *info2,
+                  const int32_t iters[3], double user_lambda, double *S12_out, int32_t *n_inliers, uint8_t *pair_state,
+                  struct sqlm_sim3_stats *stats);
+int sim3_get_pair_chi2(const Sim3Solver *s, double *chi2);
+int sim3_get_linearization(const Sim3Solver *s, double *e, double *J);
+int sim3_get_last_step(const Sim3Solver *s, int prob, double *H, double *b, double *dx);
 
 // ORB front end (sqlm_orb.hip): one engine per context, on the context's stream.
 struct OrbEngine;

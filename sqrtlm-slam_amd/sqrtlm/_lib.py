@@ -34,6 +34,7 @@ EXPORTS = [
     "sqlm_eg_set_problem", "sqlm_eg_optimize", "sqlm_eg_get_poses", "sqlm_eg_get_edge_chi2",
     "sqlm_eg_get_jacobians", "sqlm_eg_get_last_step", "sqlm_eg_get_exec_info",
     "sqlm_get_rcs_layout", "sqlm_get_exec_info", "sqlm_get_last_step",
+    "sqlm_sim3_optimize", "sqlm_sim3_get_pair_chi2", "sqlm_sim3_get_linearization", "sqlm_sim3_get_last_step",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -70,6 +71,30 @@ class Stats(C.Structure):
                     trace_lambda=list(self.trace_lambda[:n]), trace_trials=list(self.trace_trials[:n]),
                     ms_total=self.ms_total, ms_setup=self.ms_setup, ms_linearize=self.ms_linearize,
                     ms_trials=self.ms_trials)
+
+
+SIM3_TRACE_MAX = 16
+
+
+class Sim3Stats(C.Structure):
+    """sqlm_sim3_stats: one per problem of a sqlm_sim3_optimize call."""
+    _fields_ = [
+        ("n_corr", C.c_int), ("n_bad", C.c_int),
+        ("iterations", C.c_int * 2), ("trials", C.c_int * 2), ("result", C.c_int * 2),
+        ("chi2_begin", C.c_double * 2), ("chi2_end", C.c_double * 2), ("lambda_end", C.c_double * 2),
+        ("trace_len", C.c_int * 2),
+        ("trace_chi2", (C.c_double * SIM3_TRACE_MAX) * 2), ("trace_lambda", (C.c_double * SIM3_TRACE_MAX) * 2),
+        ("trace_trials", (C.c_int * SIM3_TRACE_MAX) * 2),
+    ]
+
+    def as_dict(self) -> dict:
+        n = list(self.trace_len)
+        return dict(n_corr=self.n_corr, n_bad=self.n_bad, iterations=list(self.iterations), trials=list(self.trials),
+                    result=list(self.result), chi2_begin=list(self.chi2_begin), chi2_end=list(self.chi2_end),
+                    lambda_end=list(self.lambda_end),
+                    trace_chi2=[list(self.trace_chi2[s][:n[s]]) for s in range(2)],
+                    trace_lambda=[list(self.trace_lambda[s][:n[s]]) for s in range(2)],
+                    trace_trials=[list(self.trace_trials[s][:n[s]]) for s in range(2)])
 
 
 _lib = None

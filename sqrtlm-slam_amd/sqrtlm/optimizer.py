@@ -8,6 +8,7 @@ schedule on the MI355X through libsqrtlm.so:
 * ``LocalBundleAdjustment``  -> g2oOptimizer.cc:704-1191 (3 passes, outlier tags)
 * ``GlobalBundleAdjustemnt`` -> g2oOptimizer.cc:80-89 (the reference's spelling)
 * ``BundleAdjustment``       -> g2oOptimizer.cc:110-362
+* ``OptimizeSim3``           -> g2oOptimizer.cc:1560-1793 (batched: ``Context.sim3_optimize``)
 
 Results are written back into the problem (poses, points) like the
 reference's ``SetPose`` / ``SetWorldPos`` write-back (g2oOptimizer.cc:1167-1189).
@@ -267,6 +268,46 @@ class Context:
         check(lib().sqlm_eg_get_last_step(self._h, ptr(b), ptr(dx)), "sqlm_eg_get_last_step")
         return b, dx
 
+    # ------------------------------------------------------------- Sim3 alignment
+    def sim3_optimize(self, problems, iters=None, user_lambda: float = 0.0):
+        """sqlm_sim3_optimize on a list of sim3.Sim3Problem, all in one launch.
+        Returns (S12_out (P,8), n_inliers (P,), pair_state (n_pair,) in batch
+        order, [stats dict per problem]); ``self.sim3_pair_off`` keeps the
+        batch's CSR offsets for the introspection calls."""
+        from . import sim3 as _s3
+        a = _s3.pack(problems)
+        P, n = len(problems), int(a["pair_off"][-1])
+        S_out, n_in = np.zeros((P, 8)), np.zeros(P, np.int32)
+        state = np.zeros(n, np.uint8)
+        st = (_lib.Sim3Stats * max(P, 1))()
+        it = None if iters is None else np.ascontiguousarray(iters, np.int32).reshape(3)
+        check(lib().sqlm_sim3_optimize(
+            self._h, P, ptr(a["S12"]), ptr(a["intr1"]), ptr(a["intr2"]), ptr(a["fix_scale"]), ptr(a["th2"]),
+            ptr(a["pair_off"]), ptr(a["X1c"]), ptr(a["X2c"]), ptr(a["obs1"]), ptr(a["obs2"]), ptr(a["info1"]),
+            ptr(a["info2"]), ptr(it), C.c_double(user_lambda), ptr(S_out), ptr(n_in), ptr(state), st),
+            "sqlm_sim3_optimize")
+        self.sim3_pair_off = a["pair_off"]
+        return S_out, n_in, state, [st[k].as_dict() for k in range(P)]
+
+    def sim3_pair_chi2(self):
+        """(n_pair, 2 checks, 2 edges): the chi2 values the two threshold tests read."""
+        out = np.zeros((int(self.sim3_pair_off[-1]), 2, 2))
+        check(lib().sqlm_sim3_get_pair_chi2(self._h, ptr(out)), "sqlm_sim3_get_pair_chi2")
+        return out
+
+    def sim3_linearization(self):
+        """e (n_pair, 2 edges, 2), J (n_pair, 2 edges, 2, 7) at the input S12 of the last call."""
+        n = int(self.sim3_pair_off[-1])
+        e, J = np.zeros((n, 2, 2)), np.zeros((n, 2, 2, 7))
+        check(lib().sqlm_sim3_get_linearization(self._h, ptr(e), ptr(J)), "sqlm_sim3_get_linearization")
+        return e, J
+
+    def sim3_last_step(self, prob: int = 0):
+        """H (7,7), b (7,), dx (7,) of problem ``prob``'s last LM trial: (H + lambda I) dx = b."""
+        H, b, dx = np.zeros((7, 7)), np.zeros(7), np.zeros(7)
+        check(lib().sqlm_sim3_get_last_step(self._h, int(prob), ptr(H), ptr(b), ptr(dx)), "sqlm_sim3_get_last_step")
+        return H, b, dx
+
 
 def comm_unique_id() -> bytes:
     n = lib().sqlm_comm_id_size()
@@ -368,3 +409,25 @@ class Optimizer:
         n, st = c.eg_optimize(20, 1e-16, stop_flag)
         pg.Siw[:] = c.eg_poses()
         return n, st
+
+    @classmethod
+    def OptimizeSim3(cls, prob, th2: float | None = None, bFixScale: bool | None = None, ctx: Context | None = None):
+        """g2oOptimizer::OptimizeSim3 (g2oOptimizer.cc:1560-1793) on an assembled
+        sim3.Sim3Problem: the pairs still ``matched`` are aligned, ``prob.S12``
+        receives the optimised Sim3 (unchanged when fewer than 10 pairs survive
+        the first stage), rejected pairs are cleared from ``prob.matched`` like
+        ``vpMatches1[idx] = NULL``, and the inlier count nIn is returned."""
+        c = cls._context(ctx)
+        idx = np.nonzero(prob.matched)[0]
+        sub = prob.copy()
+        for k in ("X1c", "X2c", "obs1", "obs2", "info1", "info2"):
+            setattr(sub, k, np.ascontiguousarray(getattr(prob, k)[idx]))
+        sub.matched = np.ones(idx.size, bool)
+        if th2 is not None:
+            sub.th2 = float(np.float32(th2))
+        if bFixScale is not None:
+            sub.fix_scale = bool(bFixScale)
+        S, n_in, state, _ = c.sim3_optimize([sub])
+        prob.S12[:] = S[0]
+        prob.matched[idx[state != 0]] = False
+        return int(n_in[0])

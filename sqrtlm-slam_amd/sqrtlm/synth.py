@@ -578,6 +578,12 @@ def make_pose_graph(n_kf: int = 200, *, window: int = 4, n_loops: int = 3, seed:
                      meta=dict(gt=gt, seed=seed))
 
 
+def make_sim3_problem(*args, **kw):
+    """Two views of points with a known S12 for OptimizeSim3: see sim3.make_sim3_problem."""
+    from .sim3 import make_sim3_problem as make
+    return make(*args, **kw)
+
+
 # ---- synthetic grey images for the ORB front end (SURVEY.md §8 f3) ----------
 
 def make_scene(w: int, h: int, *, seed: int = 0, n_rect: int = 0, n_disk: int = 0) -> np.ndarray:
