@@ -2,8 +2,8 @@
 //
 // Drop-in sibling of g2oOptimizer (src/backend/g2oOptimizer.cc) for the
 // calls the MI355X backend implements: LocalBundleAdjustment,
-// BundleAdjustment, GlobalBundleAdjustemnt, OptimizeEssentialGraph and
-// OptimizeSim3 (include/backend/Optimizer.h:50-69).
+// BundleAdjustment, GlobalBundleAdjustemnt, OptimizeEssentialGraph,
+// OptimizeSim3 and PoseOptimization (include/backend/Optimizer.h:50-69).
 // It is meant to be added to the reference tree as include/backend/hipOptimizer.h
 // + src/backend/hipOptimizer.cc and selected in Optimizer.cc's dispatch
 // (see INTEGRATION.md §4); it builds against the reference's own headers and
@@ -22,6 +22,8 @@
 
 #include "Eigen/Core"
 #include "LoopClosing.h"
+#include "pcl/kdtree/kdtree_flann.h"
+#include "point_types.h"
 
 // global, as in the reference (include/utils/lidarconfig.h:7 declares it
 // outside namespace ORB_SLAM2; a forward declaration inside the namespace
@@ -33,6 +35,7 @@ namespace ORB_SLAM2 {
 class KeyFrame;
 class MapPoint;
 class Map;
+class Frame;
 
 class hipOptimizer {
  public:
@@ -56,6 +59,15 @@ class hipOptimizer {
   // count, updates g2oS12 and clears the rejected entries of vpMatches1.
   static int OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, std::vector<MapPoint*>& vpMatches1,
                           g2o::Sim3& g2oS12, const float th2, const bool bFixScale);
+  // g2oOptimizer::PoseOptimization (g2oOptimizer.cc:385-679) on the GPU
+  // (sqlm_pose_optimize / sqlm_pose_refine_lidar, adapter/hipOptimizerPose.cc):
+  // sets the frame's pose and the counted keypoints' mvbOutlier, returns the
+  // inlier count. Tree is never given: the default makes this the reference's
+  // signature (g2oOptimizer.h:136-137), and keeps the kd-tree's pointer type a
+  // dependent name for translation units that never call it.
+  template <typename Tree = pcl::KdTreeFLANN<PointI> >
+  static int PoseOptimization(Frame* pFrame, PointICloudPtr local_lidarmap_cloud_ptr,
+                              typename Tree::Ptr kdtree_local_map, const lidarConfig* lidarconfig);
 
   // Capture mode around the g2o backend (Optimizer.cc dispatch): Begin*
   // records the seam inputs, End* the g2o write-back, then the file is written.

@@ -216,6 +216,81 @@ int sqlm_sim3_get_pair_chi2(sqlm_ctx *ctx, double *chi2);
 int sqlm_sim3_get_linearization(sqlm_ctx *ctx, double *e, double *J);
 int sqlm_sim3_get_last_step(sqlm_ctx *ctx, int prob, double *H, double *b, double *dx);
 
+/* Motion-only bundle adjustment: g2oOptimizer::PoseOptimization
+ * (g2oOptimizer.cc:385-679), n_prob independent problems in one call (Tracking's
+ * call is n_prob = 1, Relocalization's candidates are a batch). One free
+ * VertexSE3Expmap per problem and one EdgeSE3ProjectXYZOnlyPose per monocular
+ * correspondence ("edge"): e = uv - cam_project(T_cw Xw), information info * I2,
+ * analytic Jacobian, Huber delta (double)(float)sqrt(th2).
+ * sqlm_pose_optimize runs the vision schedule. Fewer than 3 edges: n_inliers =
+ * 0, the pose is returned unchanged, flags 0. Otherwise four rounds; round r
+ * restarts from the INPUT pose, runs optimize(iters[r]) over the level-0 edges
+ * (no such edge or iters[r] = 0: no trial, no error computed) and then
+ * classifies every edge: a level-1 edge is evaluated at the round's estimate,
+ * a level-0 edge keeps the error last computed (it may belong to a rejected
+ * trial); (float)chi2 > (float)th2 puts the edge on level 1 (outlier), else on
+ * level 0. Rounds 0-2 run with the Huber kernel, round 3 without; with fewer
+ * than 10 edges only round 0 runs. The final classification reads the errors
+ * in the same way and tests (double)(float)chi2 > th2: outlier[] holds its
+ * flags, n_inliers = n_corr - their number; the pose is the last round's.
+ * sqlm_pose_refine_lidar is the optional LiDAR stage (:560-641) and the final
+ * classification after it: one optimize(iters) from the given pose (the
+ * caller passes it after its own float round trip, SetPose / toSE3Quat) over
+ * the mono edges with outlier_in = 0 plus every LiDAR edge on the same
+ * vertex: kind 0 EdgeLidarFlatPoint e = (T_cw pw - pc) . n, kind 1
+ * EdgeLidarCornerPoint e = |T_cw pw - pc| (lid_n ignored); scalar information,
+ * no robust kernel, numeric Jacobians (central differences through oplus,
+ * delta 1e-9). robust_on[p] = 1 keeps the Huber kernel on problem p's mono
+ * edges (fewer than 10 correspondences never reach the round that removes it).
+ * The whole schedule of every problem runs in one kernel launch. */
+#define SQLM_POSE_STAGES 5 /* rounds 0-3, LiDAR stage */
+#define SQLM_POSE_CHECKS 5 /* the checks after rounds 0-3, the final classification */
+typedef struct sqlm_pose_stats {
+  int n_corr, rounds; /* edges of the problem; rounds run (0, 1 or 4; 0 from a refine) */
+  int n_bad[4];       /* level-1 edges after each round's check */
+  int n_lidar, n_bad_final;
+  int iterations[SQLM_POSE_STAGES], trials[SQLM_POSE_STAGES], result[SQLM_POSE_STAGES]; /* as in sqlm_stats */
+  int active[SQLM_POSE_STAGES];                        /* level-0 edges the stage optimized (LiDAR edges included) */
+  double chi2_begin[SQLM_POSE_STAGES], chi2_end[SQLM_POSE_STAGES], lambda_end[SQLM_POSE_STAGES];
+} sqlm_pose_stats;
+int sqlm_pose_optimize(sqlm_ctx *ctx, int n_prob,
+    const double *pose_q, const double *pose_t, /* [n_prob][4] qx qy qz qw, [n_prob][3]: T_cw                */
+    const double *intr,           /* [n_prob][4] fx fy cx cy                                           */
+    const int64_t *obs_off,       /* [n_prob+1] CSR offsets into the edge arrays                       */
+    const double *Xw,             /* [n_obs][3] pMP->GetWorldPos()                                     */
+    const double *uv,             /* [n_obs][2] kpUn.pt                                                */
+    const double *info,           /* [n_obs] mvInvLevelSigma2[kpUn.octave]                             */
+    const int32_t iters[4],       /* NULL = {10, 10, 10, 10}                                           */
+    double th2,                   /* 5.991 in the reference                                            */
+    double user_lambda,           /* 0 = g2o's computeLambdaInit (the reference); >0 for tests         */
+    double *pose_q_out, double *pose_t_out, int32_t *n_inliers, uint8_t *outlier, sqlm_pose_stats *stats);
+int sqlm_pose_refine_lidar(sqlm_ctx *ctx, int n_prob,
+    const double *pose_q, const double *pose_t, const double *intr, const int64_t *obs_off,
+    const double *Xw, const double *uv, const double *info,
+    const uint8_t *outlier_in,    /* [n_obs] 1 = level-1 edge (sqlm_pose_optimize's outlier)           */
+    const uint8_t *robust_on,     /* [n_prob]                                                          */
+    const int64_t *lid_off,       /* [n_prob+1] CSR offsets into the LiDAR arrays                      */
+    const uint8_t *lid_kind,      /* [n_lid] 0 flat, 1 corner                                          */
+    const double *lid_pc, const double *lid_pw, const double *lid_n, /* [n_lid][3] point in the camera
+                                     frame, its nearest map point in the world, the flat point's normal */
+    const double *lid_info,       /* [n_lid]                                                           */
+    const int32_t *iters,         /* one value >= 1, NULL = 10                                         */
+    double th2, double user_lambda,
+    double *pose_q_out, double *pose_t_out, int32_t *n_inliers, uint8_t *outlier, sqlm_pose_stats *stats);
+/* Introspection of the context's last sqlm_pose_optimize / sqlm_pose_refine_lidar
+ * (tests; no reference counterpart); SQLM_ERR_STATE before any call.
+ * chi2 [n_obs][SQLM_POSE_CHECKS]: the e->chi2() value each check read (a check
+ * that did not run leaves 0; a refine fills the last column only).
+ * e [n_obs][2], J [n_obs][2][6] of the mono edges and lid_e [n_lid], lid_J
+ * [n_lid][6] of the LiDAR edges (refine only) at the input pose; any may be NULL.
+ * The last LM trial of problem `prob`, in g2o's convention (H + lambda I) dx
+ * = b with b = -J^T rho' Omega e: H [36] row-major (undamped), b [6], dx [6]
+ * (zero if the damped system met a non-positive pivot); SQLM_ERR_STATE if the
+ * problem ran no trial. */
+int sqlm_pose_get_edge_chi2(sqlm_ctx *ctx, double *chi2);
+int sqlm_pose_get_linearization(sqlm_ctx *ctx, double *e, double *J, double *lid_e, double *lid_J);
+int sqlm_pose_get_last_step(sqlm_ctx *ctx, int prob, double *H, double *b, double *dx);
+
 /* Results (write-back inputs, g2oOptimizer.cc:1167-1189, :306-360). */
 int sqlm_get_poses(sqlm_ctx *ctx, double *pose_q, double *pose_t);
 int sqlm_get_points(sqlm_ctx *ctx, double *pt);

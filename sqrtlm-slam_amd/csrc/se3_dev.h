@@ -155,6 +155,62 @@ SQLM_HD void lidar_jacobian(const double q[4], const double t[3], const double *
   }
 }
 
+// EdgeLidarCornerPoint error (types_six_dof_expmap.h:237-262) restated as
+// || T_cw p_w - p_c ||
+SQLM_HD double lidar_corner_error(const double q[4], const double t[3], const double *pc, const double *pw) {
+  double c[3];
+  q_rotate(q, pw, c);
+  const double d0 = (c[0] + t[0]) - pc[0], d1 = (c[1] + t[1]) - pc[1], d2 = (c[2] + t[2]) - pc[2];
+  return sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+}
+
+// its numeric central-difference Jacobian, as lidar_jacobian
+SQLM_HD void lidar_corner_jacobian(const double q[4], const double t[3], const double *pc, const double *pw,
+                                   double J[6]) {
+  const double delta = 1e-9, scalar = 1.0 / (2 * delta);
+  for (int k = 0; k < 6; ++k) {
+    double add[6] = {0, 0, 0, 0, 0, 0};
+    double qa[4] = {q[0], q[1], q[2], q[3]}, ta[3] = {t[0], t[1], t[2]};
+    add[k] = delta;
+    se3_oplus(qa, ta, add);
+    const double e1 = lidar_corner_error(qa, ta, pc, pw);
+    double qb[4] = {q[0], q[1], q[2], q[3]}, tb[3] = {t[0], t[1], t[2]};
+    add[k] = -delta;
+    se3_oplus(qb, tb, add);
+    const double e2 = lidar_corner_error(qb, tb, pc, pw);
+    J[k] = scalar * (e1 - e2);
+  }
+}
+
+// EdgeSE3ProjectXYZOnlyPose (types_six_dof_expmap.h:153-157, .cpp:290-296):
+// xc = q X + t, e = uv - (fx x / z + cx, fy y / z + cy), K = fx fy cx cy
+SQLM_HD void pose_mono_error(const double q[4], const double t[3], const double K[4], const double X[3],
+                             const double uv[2], double xc[3], double e[2]) {
+  double r[3];
+  q_rotate(q, X, r);
+  xc[0] = r[0] + t[0]; xc[1] = r[1] + t[1]; xc[2] = r[2] + t[2];
+  e[0] = uv[0] - ((xc[0] / xc[2]) * K[0] + K[2]);
+  e[1] = uv[1] - ((xc[1] / xc[2]) * K[1] + K[3]);
+}
+
+// its analytic Jacobian d e / d [omega; upsilon] (types_six_dof_expmap.cpp:266-288)
+SQLM_HD void pose_mono_jacobian(const double xc[3], const double K[4], double J[12]) {
+  const double x = xc[0], y = xc[1], invz = 1.0 / xc[2], invz_2 = invz * invz;
+  const double fx = K[0], fy = K[1];
+  J[0] = ((x * y) * invz_2) * fx;
+  J[1] = -(1 + ((x * x) * invz_2)) * fx;
+  J[2] = (y * invz) * fx;
+  J[3] = -invz * fx;
+  J[4] = 0;
+  J[5] = (x * invz_2) * fx;
+  J[6] = (1 + (y * y) * invz_2) * fy;
+  J[7] = ((-x * y) * invz_2) * fy;
+  J[8] = (-x * invz) * fy;
+  J[9] = 0;
+  J[10] = -invz * fy;
+  J[11] = (y * invz_2) * fy;
+}
+
 #pragma clang fp contract(on)
 
 }  // namespace sqlm

@@ -214,6 +214,7 @@ struct sqlm_ctx {
   bool need_maxdiag = false;
   EGSolver *eg = nullptr;
   Sim3Solver *sim3 = nullptr;
+  PoseSolver *pose = nullptr;
   OrbEngine *orb = nullptr;
   // ---- timing ----
   hipEvent_t ev[2 * SQLM_NKERNEL_TIMERS] = {};
@@ -2446,6 +2447,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   comm_destroy(c->comm);
   if (c->eg) eg_destroy(c->eg);
   if (c->sim3) sim3_destroy(c->sim3);
+  if (c->pose) pose_destroy(c->pose);
   if (c->orb) orb_destroy(c->orb);
   for (auto &b : c->bufs)
     if (b.p) (void)hipFree(b.p);
@@ -2700,6 +2702,92 @@ int sqlm_sim3_get_last_step(sqlm_ctx *c, int prob, double *H, double *b, double 
   if (!c || !H || !b || !dx) return SQLM_ERR_INVALID_ARG;
   if (!c->sim3) return SQLM_ERR_STATE;
   return sim3_get_last_step(c->sim3, prob, H, b, dx);
+}
+
+namespace {
+
+// the argument checks sqlm_pose_optimize and sqlm_pose_refine_lidar share
+int pose_args_ok(const sqlm_ctx *c, const PoseArgs &a) {
+  if (!c || a.n_prob < 0 || !a.obs_off) return 0;
+  if (!(a.th2 > 0.0) || !(a.user_lambda >= 0.0)) return 0;
+  for (int k = 0; k < 5; ++k)
+    if (a.iters[k] < 0) return 0;
+  if (a.refine && (!a.lid_off || a.iters[4] < 1)) return 0;
+  if (a.n_prob > 0 && (!a.pose_q || !a.pose_t || !a.intr || !a.pose_q_out || !a.pose_t_out || !a.n_inliers)) return 0;
+  if (a.n_prob > 0 && a.refine && !a.robust_on) return 0;
+  if (a.obs_off[0] < 0 || (a.refine && a.lid_off[0] < 0)) return 0;
+  for (int k = 0; k < a.n_prob; ++k) {
+    if (a.obs_off[k + 1] < a.obs_off[k] || a.obs_off[k + 1] - a.obs_off[k] > INT32_MAX) return 0;
+    if (a.refine && (a.lid_off[k + 1] < a.lid_off[k] || a.lid_off[k + 1] - a.lid_off[k] > INT32_MAX)) return 0;
+  }
+  if (a.obs_off[a.n_prob] > a.obs_off[0] && (!a.Xw || !a.uv || !a.info || !a.outlier || (a.refine && !a.outlier_in)))
+    return 0;
+  if (a.refine && a.lid_off[a.n_prob] > a.lid_off[0] && (!a.lid_kind || !a.lid_pc || !a.lid_pw || !a.lid_n || !a.lid_info))
+    return 0;
+  return 1;
+}
+
+int pose_call(sqlm_ctx *c, const PoseArgs &a) {
+  if (!pose_args_ok(c, a)) return SQLM_ERR_INVALID_ARG;
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  if (!c->pose && !(c->pose = pose_create(c->stream))) return SQLM_ERR_OOM;
+  return pose_run(c->pose, a);
+}
+
+}  // namespace
+
+int sqlm_pose_optimize(sqlm_ctx *c, int n_prob, const double *pose_q, const double *pose_t, const double *intr,
+                       const int64_t *obs_off, const double *Xw, const double *uv, const double *info,
+                       const int32_t iters[4], double th2, double user_lambda, double *pose_q_out, double *pose_t_out,
+                       int32_t *n_inliers, uint8_t *outlier, sqlm_pose_stats *stats) {
+  PoseArgs a;
+  a.n_prob = n_prob;
+  a.pose_q = pose_q; a.pose_t = pose_t; a.intr = intr; a.obs_off = obs_off;
+  a.Xw = Xw; a.uv = uv; a.info = info;
+  if (iters)
+    for (int k = 0; k < 4; ++k) a.iters[k] = iters[k];
+  a.th2 = th2; a.user_lambda = user_lambda;
+  a.pose_q_out = pose_q_out; a.pose_t_out = pose_t_out; a.n_inliers = n_inliers; a.outlier = outlier; a.stats = stats;
+  return pose_call(c, a);
+}
+
+int sqlm_pose_refine_lidar(sqlm_ctx *c, int n_prob, const double *pose_q, const double *pose_t, const double *intr,
+                           const int64_t *obs_off, const double *Xw, const double *uv, const double *info,
+                           const uint8_t *outlier_in, const uint8_t *robust_on, const int64_t *lid_off,
+                           const uint8_t *lid_kind, const double *lid_pc, const double *lid_pw, const double *lid_n,
+                           const double *lid_info, const int32_t *iters, double th2, double user_lambda,
+                           double *pose_q_out, double *pose_t_out, int32_t *n_inliers, uint8_t *outlier,
+                           sqlm_pose_stats *stats) {
+  PoseArgs a;
+  a.n_prob = n_prob;
+  a.refine = 1;
+  a.pose_q = pose_q; a.pose_t = pose_t; a.intr = intr; a.obs_off = obs_off;
+  a.Xw = Xw; a.uv = uv; a.info = info;
+  a.outlier_in = outlier_in; a.robust_on = robust_on;
+  a.lid_off = lid_off; a.lid_kind = lid_kind; a.lid_pc = lid_pc; a.lid_pw = lid_pw; a.lid_n = lid_n;
+  a.lid_info = lid_info;
+  if (iters) a.iters[4] = iters[0];
+  a.th2 = th2; a.user_lambda = user_lambda;
+  a.pose_q_out = pose_q_out; a.pose_t_out = pose_t_out; a.n_inliers = n_inliers; a.outlier = outlier; a.stats = stats;
+  return pose_call(c, a);
+}
+
+int sqlm_pose_get_edge_chi2(sqlm_ctx *c, double *chi2) {
+  if (!c || !chi2) return SQLM_ERR_INVALID_ARG;
+  if (!c->pose) return SQLM_ERR_STATE;
+  return pose_get_edge_chi2(c->pose, chi2);
+}
+
+int sqlm_pose_get_linearization(sqlm_ctx *c, double *e, double *J, double *lid_e, double *lid_J) {
+  if (!c || (!e && !J && !lid_e && !lid_J)) return SQLM_ERR_INVALID_ARG;
+  if (!c->pose) return SQLM_ERR_STATE;
+  return pose_get_linearization(c->pose, e, J, lid_e, lid_J);
+}
+
+int sqlm_pose_get_last_step(sqlm_ctx *c, int prob, double *H, double *b, double *dx) {
+  if (!c || !H || !b || !dx) return SQLM_ERR_INVALID_ARG;
+  if (!c->pose) return SQLM_ERR_STATE;
+  return pose_get_last_step(c->pose, prob, H, b, dx);
 }
 
 int sqlm_global_ba(sqlm_ctx *c, int iterations, const volatile uint8_t *stop, sqlm_stats *st, int *n_iter) {

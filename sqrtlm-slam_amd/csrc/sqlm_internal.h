@@ -449,6 +449,57 @@ int sim3_get_pair_chi2(const Sim3Solver *s, double *chi2);
 int sim3_get_linearization(const Sim3Solver *s, double *e, double *J);
 int sim3_get_last_step(const Sim3Solver *s, int prob, double *H, double *b, double *dx);
 
+// Batched motion-only BA (sqlm_pose.cpp host, sqlm_pose.hip kernel): one
+// solver per context, on the context's stream; its buffers are reused.
+constexpr int kPoseChecks = 5;   // 4 rounds + the final classification
+constexpr int kPoseStepLen = 56;  // H 36, b 6, dx 6, lambda, valid
+struct PoseDev {  // device pointers of one sqlm_pose_optimize / sqlm_pose_refine_lidar call
+  int n_prob = 0;
+  int refine = 0;                      // 0: the four vision rounds, 1: the LiDAR stage
+  int iters[5] = {10, 10, 10, 10, 10};  // rounds 0-3, LiDAR stage
+  double user_lambda = 0.0, th2 = 5.991;
+  const double *pose = nullptr, *intr = nullptr;  // [n_prob][8] q t 0, [n_prob][4]
+  const int64_t *obs_off = nullptr;               // [n_prob+1]
+  const double *Xw = nullptr, *uv = nullptr, *info = nullptr;
+  const uint8_t *outlier_in = nullptr;            // [n_obs] (refine)
+  const uint8_t *robust_on = nullptr;             // [n_prob] (refine)
+  const int64_t *lid_off = nullptr;               // [n_prob+1] (refine)
+  const uint8_t *lid_kind = nullptr;
+  const double *lid_pc = nullptr, *lid_pw = nullptr, *lid_n = nullptr, *lid_info = nullptr;
+  double *pose_out = nullptr;             // [n_prob][8]
+  int32_t *n_inliers = nullptr;           // [n_prob]
+  uint8_t *outlier = nullptr;             // [n_obs] level of every mono edge (refine: preset to outlier_in)
+  struct sqlm_pose_stats *stats = nullptr;
+  double *edge_chi2 = nullptr;            // [n_obs][kPoseChecks]
+  double *lin_e = nullptr, *lin_J = nullptr;  // [n_obs][2], [n_obs][2][6]
+  double *lid_e = nullptr, *lid_J = nullptr;  // [n_lid], [n_lid][6]
+  double *last_step = nullptr;            // [n_prob][kPoseStepLen]
+};
+void launch_pose(const PoseDev &d, hipStream_t st);
+struct PoseSolver;
+PoseSolver *pose_create(hipStream_t st);
+void pose_destroy(PoseSolver *s);
+struct PoseArgs {  // host pointers of one call (see include/sqrtlm.h)
+  int n_prob = 0, refine = 0;
+  const double *pose_q = nullptr, *pose_t = nullptr, *intr = nullptr;
+  const int64_t *obs_off = nullptr;
+  const double *Xw = nullptr, *uv = nullptr, *info = nullptr;
+  const uint8_t *outlier_in = nullptr, *robust_on = nullptr;
+  const int64_t *lid_off = nullptr;
+  const uint8_t *lid_kind = nullptr;
+  const double *lid_pc = nullptr, *lid_pw = nullptr, *lid_n = nullptr, *lid_info = nullptr;
+  int iters[5] = {10, 10, 10, 10, 10};
+  double th2 = 5.991, user_lambda = 0.0;
+  double *pose_q_out = nullptr, *pose_t_out = nullptr;
+  int32_t *n_inliers = nullptr;
+  uint8_t *outlier = nullptr;
+  struct sqlm_pose_stats *stats = nullptr;
+};
+int pose_run(PoseSolver *s, const PoseArgs &a);
+int pose_get_edge_chi2(const PoseSolver *s, double *chi2);
+int pose_get_linearization(const PoseSolver *s, double *e, double *J, double *lid_e, double *lid_J);
+int pose_get_last_step(const PoseSolver *s, int prob, double *H, double *b, double *dx);
+
 // ORB front end (sqlm_orb.hip): one engine per context, on the context's stream.
 struct OrbEngine;
 OrbEngine *orb_create(hipStream_t st);

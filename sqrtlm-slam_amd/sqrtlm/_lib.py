@@ -35,6 +35,8 @@ EXPORTS = [
     "sqlm_eg_get_jacobians", "sqlm_eg_get_last_step", "sqlm_eg_get_exec_info",
     "sqlm_get_rcs_layout", "sqlm_get_exec_info", "sqlm_get_last_step",
     "sqlm_sim3_optimize", "sqlm_sim3_get_pair_chi2", "sqlm_sim3_get_linearization", "sqlm_sim3_get_last_step",
+    "sqlm_pose_optimize", "sqlm_pose_refine_lidar", "sqlm_pose_get_edge_chi2", "sqlm_pose_get_linearization",
+    "sqlm_pose_get_last_step",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -95,6 +97,28 @@ class Sim3Stats(C.Structure):
                     trace_chi2=[list(self.trace_chi2[s][:n[s]]) for s in range(2)],
                     trace_lambda=[list(self.trace_lambda[s][:n[s]]) for s in range(2)],
                     trace_trials=[list(self.trace_trials[s][:n[s]]) for s in range(2)])
+
+
+POSE_STAGES = 5  # rounds 0-3, LiDAR stage
+POSE_CHECKS = 5  # the checks after rounds 0-3, the final classification
+
+
+class PoseStats(C.Structure):
+    """sqlm_pose_stats: one per problem of a sqlm_pose_optimize / sqlm_pose_refine_lidar call."""
+    _fields_ = [
+        ("n_corr", C.c_int), ("rounds", C.c_int), ("n_bad", C.c_int * 4),
+        ("n_lidar", C.c_int), ("n_bad_final", C.c_int),
+        ("iterations", C.c_int * POSE_STAGES), ("trials", C.c_int * POSE_STAGES), ("result", C.c_int * POSE_STAGES),
+        ("active", C.c_int * POSE_STAGES),
+        ("chi2_begin", C.c_double * POSE_STAGES), ("chi2_end", C.c_double * POSE_STAGES),
+        ("lambda_end", C.c_double * POSE_STAGES),
+    ]
+
+    def as_dict(self) -> dict:
+        return dict(n_corr=self.n_corr, rounds=self.rounds, n_bad=list(self.n_bad), n_lidar=self.n_lidar,
+                    n_bad_final=self.n_bad_final, iterations=list(self.iterations), trials=list(self.trials),
+                    result=list(self.result), active=list(self.active), chi2_begin=list(self.chi2_begin),
+                    chi2_end=list(self.chi2_end), lambda_end=list(self.lambda_end))
 
 
 _lib = None

@@ -9,6 +9,8 @@ schedule on the MI355X through libsqrtlm.so:
 * ``GlobalBundleAdjustemnt`` -> g2oOptimizer.cc:80-89 (the reference's spelling)
 * ``BundleAdjustment``       -> g2oOptimizer.cc:110-362
 * ``OptimizeSim3``           -> g2oOptimizer.cc:1560-1793 (batched: ``Context.sim3_optimize``)
+* ``PoseOptimization``       -> g2oOptimizer.cc:385-679 (batched: ``Context.pose_optimize`` /
+  ``Context.pose_refine_lidar``)
 
 Results are written back into the problem (poses, points) like the
 reference's ``SetPose`` / ``SetWorldPos`` write-back (g2oOptimizer.cc:1167-1189).
@@ -308,6 +310,87 @@ class Context:
         check(lib().sqlm_sim3_get_last_step(self._h, int(prob), ptr(H), ptr(b), ptr(dx)), "sqlm_sim3_get_last_step")
         return H, b, dx
 
+    # ------------------------------------------------------------- motion-only BA
+    def _pose_out(self, a, P):
+        n = int(a["obs_off"][-1])
+        return (np.zeros((P, 4)), np.zeros((P, 3)), np.zeros(P, np.int32), np.zeros(n, np.uint8),
+                (_lib.PoseStats * max(P, 1))())
+
+    def pose_optimize(self, problems, iters=None, user_lambda: float = 0.0, th2: float | None = None):
+        """sqlm_pose_optimize on a list of pose.PoseProblem, all in one launch
+        (``th2``: the problems' own, which must agree). Returns (pose_q (P,4),
+        pose_t (P,3), n_inliers (P,), outlier (n_obs,) in batch order, [stats
+        dict per problem]); ``self.pose_obs_off`` / ``self.pose_lid_off`` keep
+        the batch's CSR offsets for the introspection calls."""
+        from . import pose as _p
+        a = _p.pack(problems)
+        P = len(problems)
+        th2 = self._pose_th2(problems, th2)
+        q, t, n_in, flag, st = self._pose_out(a, P)
+        it = None if iters is None else np.ascontiguousarray(iters, np.int32).reshape(4)
+        check(lib().sqlm_pose_optimize(
+            self._h, P, ptr(a["pose_q"]), ptr(a["pose_t"]), ptr(a["intr"]), ptr(a["obs_off"]), ptr(a["Xw"]),
+            ptr(a["uv"]), ptr(a["info"]), ptr(it), C.c_double(th2), C.c_double(user_lambda), ptr(q), ptr(t),
+            ptr(n_in), ptr(flag), st), "sqlm_pose_optimize")
+        self.pose_obs_off, self.pose_lid_off = a["obs_off"], np.zeros(P + 1, np.int64)
+        return q, t, n_in, flag, [st[k].as_dict() for k in range(P)]
+
+    @staticmethod
+    def _pose_th2(problems, th2):
+        if th2 is not None:
+            return float(th2)
+        ths = {float(p.th2) for p in problems}
+        if len(ths) > 1:
+            raise ValueError("the problems of one call share th2")
+        return ths.pop() if ths else 5.991
+
+    def pose_refine_lidar(self, problems, lidar, outlier_in, robust_on=None, iters: int | None = None,
+                          user_lambda: float = 0.0, th2: float | None = None):
+        """sqlm_pose_refine_lidar: the LiDAR stage and the final classification
+        on a list of pose.PoseProblem (their poses are the stage's start: pass
+        them after the float round trip) with one pose.LidarPairs each.
+        ``outlier_in`` (n_obs,) in batch order are the level-1 edges;
+        ``robust_on`` defaults to "fewer than 10 edges". Returns as
+        ``pose_optimize``."""
+        from . import pose as _p
+        a, l = _p.pack(problems), _p.pack_lidar(lidar)
+        P = len(problems)
+        if len(lidar) != P:
+            raise ValueError("one LidarPairs per problem")
+        th2 = self._pose_th2(problems, th2)
+        oin = np.ascontiguousarray(outlier_in, np.uint8).reshape(int(a["obs_off"][-1]))
+        rob = (np.array([p.n_obs < 10 for p in problems], np.uint8) if robust_on is None
+               else np.ascontiguousarray(robust_on, np.uint8).reshape(P))
+        q, t, n_in, flag, st = self._pose_out(a, P)
+        it = None if iters is None else np.array([iters], np.int32)
+        check(lib().sqlm_pose_refine_lidar(
+            self._h, P, ptr(a["pose_q"]), ptr(a["pose_t"]), ptr(a["intr"]), ptr(a["obs_off"]), ptr(a["Xw"]),
+            ptr(a["uv"]), ptr(a["info"]), ptr(oin), ptr(rob), ptr(l["lid_off"]), ptr(l["lid_kind"]), ptr(l["lid_pc"]),
+            ptr(l["lid_pw"]), ptr(l["lid_n"]), ptr(l["lid_info"]), ptr(it), C.c_double(th2), C.c_double(user_lambda),
+            ptr(q), ptr(t), ptr(n_in), ptr(flag), st), "sqlm_pose_refine_lidar")
+        self.pose_obs_off, self.pose_lid_off = a["obs_off"], l["lid_off"]
+        return q, t, n_in, flag, [st[k].as_dict() for k in range(P)]
+
+    def pose_edge_chi2(self):
+        """(n_obs, 5): the chi2 each check (after rounds 0-3, final) read."""
+        out = np.zeros((int(self.pose_obs_off[-1]), _lib.POSE_CHECKS))
+        check(lib().sqlm_pose_get_edge_chi2(self._h, ptr(out)), "sqlm_pose_get_edge_chi2")
+        return out
+
+    def pose_linearization(self):
+        """e (n_obs,2), J (n_obs,2,6), lid_e (n_lid,), lid_J (n_lid,6) at the input pose of the last call."""
+        n, m = int(self.pose_obs_off[-1]), int(self.pose_lid_off[-1])
+        e, J, le, lJ = np.zeros((n, 2)), np.zeros((n, 2, 6)), np.zeros(m), np.zeros((m, 6))
+        check(lib().sqlm_pose_get_linearization(self._h, ptr(e), ptr(J), ptr(le), ptr(lJ)),
+              "sqlm_pose_get_linearization")
+        return e, J, le, lJ
+
+    def pose_last_step(self, prob: int = 0):
+        """H (6,6), b (6,), dx (6,) of problem ``prob``'s last LM trial: (H + lambda I) dx = b."""
+        H, b, dx = np.zeros((6, 6)), np.zeros(6), np.zeros(6)
+        check(lib().sqlm_pose_get_last_step(self._h, int(prob), ptr(H), ptr(b), ptr(dx)), "sqlm_pose_get_last_step")
+        return H, b, dx
+
 
 def comm_unique_id() -> bytes:
     n = lib().sqlm_comm_id_size()
@@ -430,4 +513,28 @@ class Optimizer:
         S, n_in, state, _ = c.sim3_optimize([sub])
         prob.S12[:] = S[0]
         prob.matched[idx[state != 0]] = False
+        return int(n_in[0])
+
+    @classmethod
+    def PoseOptimization(cls, prob, lidar_assoc=None, ctx: Context | None = None):
+        """g2oOptimizer::PoseOptimization (g2oOptimizer.cc:385-679) on an assembled
+        pose.PoseProblem: the four vision rounds; then, if ``lidar_assoc`` is
+        given (it stands in for the kd-tree search: called with the pose
+        ``(q, t)`` after ``SetPose``'s float round trip, it returns the
+        pose.LidarPairs), the LiDAR stage. ``prob.pose_q`` / ``prob.pose_t``
+        receive the optimised pose after the float round trip of ``SetPose``
+        (unchanged with fewer than 3 edges), ``prob.outlier`` the final
+        ``mvbOutlier`` flags, and the inlier count is returned."""
+        c = cls._context(ctx)
+        q, t, n_in, flag, _ = c.pose_optimize([prob])
+        if prob.n_obs < 3:
+            return 0
+        q, t = pose_from_Tcw_f32(pose_to_Tcw_f32(q[0], t[0]))  # pFrame->SetPose(toCvMat(estimate))
+        if lidar_assoc is not None:
+            sub = prob.copy()
+            sub.pose_q[:], sub.pose_t[:] = q, t  # setEstimate(toSE3Quat(pFrame->mTcw))
+            q, t, n_in, flag, _ = c.pose_refine_lidar([sub], [lidar_assoc((q.copy(), t.copy()))], flag)
+            q, t = pose_from_Tcw_f32(pose_to_Tcw_f32(q[0], t[0]))
+        prob.pose_q[:], prob.pose_t[:] = q, t
+        prob.outlier[:] = flag != 0
         return int(n_in[0])

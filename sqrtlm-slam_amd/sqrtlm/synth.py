@@ -584,6 +584,12 @@ def make_sim3_problem(*args, **kw):
     return make(*args, **kw)
 
 
+def make_pose_problem(*args, **kw):
+    """Map points seen by one frame with a known pose for PoseOptimization: see pose.make_pose_problem."""
+    from .pose import make_pose_problem as make
+    return make(*args, **kw)
+
+
 # ---- synthetic grey images for the ORB front end (SURVEY.md §8 f3) ----------
 
 def make_scene(w: int, h: int, *, seed: int = 0, n_rect: int = 0, n_disk: int = 0) -> np.ndarray:
