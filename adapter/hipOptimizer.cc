@@ -1,6 +1,7 @@
 // hipOptimizer.cc — libsqrtlm behind the reference's Optimizer seam (see
 // hipOptimizer.h). Builds inside the reference tree only: it uses the
-// reference's KeyFrame / MapPoint / Map / lidarConfig types, OpenCV and PCL.
+// reference's KeyFrame / MapPoint / Map / lidarConfig types, OpenCV and PCL's
+// point clouds.
 //
 // Every call flattens the map objects into the seam graph of
 // include/sqrtlm_capture.h (float32, exactly what g2oOptimizer reads), runs
@@ -10,9 +11,6 @@
 // insertion order (point list order, then GetObservations() map order).
 #include "backend/hipOptimizer.h"
 #include "backend/g2oOptimizer.h"  // fallback for the configurations libsqrtlm does not cover
-
-#include <pcl/common/transforms.h>
-#include <pcl/kdtree/kdtree_flann.h>
 
 #include <algorithm>
 #include <atomic>
@@ -34,10 +32,6 @@
 #include "sqrtlm_capture.h"
 
 namespace ORB_SLAM2 {
-
-// Defined in src/backend/g2oOptimizer.cc:59-66 (namespace ORB_SLAM2, external
-// linkage) and declared in no reference header.
-PointI PointIRT2PointI(const PointIRT &Pirt);
 
 namespace {
 
@@ -220,54 +214,51 @@ void build_lba(KeyFrame* pKF, SeamGraph& g, std::vector<KeyFrame*>& local, std::
     }
 }
 
-// LBA pass 3 association (g2oOptimizer.cc:978-1062): the flat points of the
-// other local KFs, moved to the world by their pass-2 poses, form a kd-tree;
+// LBA pass 3 association (g2oOptimizer.cc:978-1073): the flat points of the
+// other local KFs, moved to the world by their pass-2 poses, are the map;
 // pKF's flat points, moved by its pass-2 pose, take their nearest neighbour
 // within distance_sq_threshold. Same float pose path as the reference
-// (Converter::toCvMat then cv::Mat::inv()).
-void lidar_pairs(KeyFrame* pKF, const std::vector<KeyFrame*>& local, const SeamGraph& g,
-                 const std::vector<double>& q, const std::vector<double>& t, const lidarConfig* cfg,
-                 SeamGraph& out) {
-  if (!cfg || !cfg->using_flat_point) return;  // corner points: LocalBundleAdjustment routes to g2o
-  auto world_of = [&](KeyFrame* k) {
+// (Converter::toCvMat then cv::Mat::inv()); the transform, the exact search
+// (the reference's kd-tree) and the accepted pairs' EdgeLidarFlatPoint edges
+// are libsqrtlm's (sqlm_set_lidar_from_clouds). false: the library failed.
+bool lidar_pairs(sqlm_ctx* ctx, KeyFrame* pKF, const std::vector<KeyFrame*>& local, const SeamGraph& g,
+                 const std::vector<double>& q, const std::vector<double>& t, const lidarConfig* cfg) {
+  if (!cfg || !cfg->using_flat_point) return true;  // corner points: LocalBundleAdjustment routes to g2o
+  auto Twc_of = [&](KeyFrame* k, float* out) {
     const int i = g.kf_index.at(k);
     float T[16];
     sqlm_pose_to_Tcw_f32(&q[4 * i], &t[3 * i], T);
     const cv::Mat Twc = cv::Mat(4, 4, CV_32F, T).inv();
-    Eigen::Matrix4d M = Eigen::Matrix4d::Identity();
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 4; ++c) M(r, c) = Twc.at<float>(r, c);
-    return Eigen::Affine3d(M);
+    for (int r = 0; r < 4; ++r)
+      for (int c = 0; c < 4; ++c) out[4 * r + c] = Twc.at<float>(r, c);
   };
-  PointIRTCloudPtr flat_map = PointIRTCloud().makeShared();
+  auto pack = [](const PointIRTCloud& cloud, std::vector<float>& xyz) {
+    for (size_t i = 0; i < cloud.size(); ++i) {
+      const PointIRT& p = cloud.points[i];
+      xyz.insert(xyz.end(), {p.x, p.y, p.z});
+    }
+  };
+  std::vector<int64_t> map_off{0};
+  std::vector<float> map_xyz, map_Twc;
   for (KeyFrame* k : local) {
     if (k->mnId == pKF->mnId) continue;
-    PointIRTCloud pts = k->surface_points_less_flat_;
-    pcl::transformPointCloud(pts, pts, world_of(k));
-    *flat_map += pts;
+    pack(k->surface_points_less_flat_, map_xyz);
+    map_off.push_back((int64_t)(map_xyz.size() / 3));
+    map_Twc.resize(map_Twc.size() + 16);
+    Twc_of(k, &map_Twc[map_Twc.size() - 16]);
   }
-  pcl::PointCloud<PointI>::Ptr cloud = PointICloud().makeShared();
-  for (const PointIRT& p : *flat_map) cloud->push_back(PointIRT2PointI(p));
-  if (cloud->empty()) return;
-  pcl::KdTreeFLANN<PointI> tree;
-  tree.setInputCloud(cloud);
-  PointIRTCloud cur;
-  pcl::transformPointCloud(pKF->surface_points_less_flat_, cur, world_of(pKF));
-  std::vector<int> idx;
-  std::vector<float> d2;
-  const int pose = g.kf_index.at(pKF);
-  for (size_t i = 0; i < cur.size(); ++i) {
-    tree.nearestKSearch(PointIRT2PointI(cur[i]), 1, idx, d2);
-    if (d2[0] >= cfg->distance_sq_threshold) continue;
-    const auto& pc = pKF->surface_points_less_flat_.points[i];
-    const auto& pw = cloud->points[idx[0]];
-    const auto& nm = pKF->surface_points_less_flat_normal_.points[i];
-    out.lid_pose.push_back(pose);
-    out.lid_pc.insert(out.lid_pc.end(), {pc.x, pc.y, pc.z});
-    out.lid_pw.insert(out.lid_pw.end(), {pw.x, pw.y, pw.z});
-    out.lid_n.insert(out.lid_n.end(), {nm.x, nm.y, nm.z});
-    out.lid_info.push_back(cfg->flat_optimized_weight);
-  }
+  if (map_xyz.empty()) return true;  // the reference would hand an empty cloud to the kd-tree
+  std::vector<float> cur, nrm;
+  float cur_Twc[16];
+  pack(pKF->surface_points_less_flat_, cur);
+  pack(pKF->surface_points_less_flat_normal_, nrm);
+  Twc_of(pKF, cur_Twc);
+  int64_t n_pairs = 0;
+  return report(sqlm_set_lidar_from_clouds(ctx, g.kf_index.at(pKF), (int)map_off.size() - 1, map_off.data(),
+                                           map_xyz.data(), map_Twc.data(), (int64_t)(cur.size() / 3), cur.data(),
+                                           cur_Twc, nrm.data(), cfg->flat_optimized_weight,
+                                           cfg->distance_sq_threshold, &n_pairs),
+                "sqlm_set_lidar_from_clouds");
 }
 
 // ---------------------------------------------------------------- capture
@@ -350,12 +341,7 @@ void hipOptimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* p
   }
   // pass 3 (:978-1114): LiDAR flat pairs at the pass-2 poses, 20 iterations
   sqlm_get_poses(ctx, q.data(), t.data());
-  SeamGraph lid;
-  lidar_pairs(pKF, local, g, q, t, cfg, lid);
-  if (!lid.lid_pose.empty())
-    report(sqlm_set_lidar(ctx, (int64_t)lid.lid_pose.size(), lid.lid_pose.data(), lid.lid_pc.data(),
-                          lid.lid_pw.data(), lid.lid_n.data(), lid.lid_info.data()),
-           "sqlm_set_lidar");
+  if (!lidar_pairs(ctx, pKF, local, g, q, t, cfg)) return;
   if (!report(sqlm_optimize(ctx, 0, 20, 0.0, stop_ptr(pbStopFlag), &st, &n), "pass 3")) return;
   // outliers (:1119-1136) and write-back under the map mutex (:1145-1189)
   sqlm_get_edge_chi2(ctx, chi2.data());

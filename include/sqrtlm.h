@@ -291,6 +291,48 @@ int sqlm_pose_get_edge_chi2(sqlm_ctx *ctx, double *chi2);
 int sqlm_pose_get_linearization(sqlm_ctx *ctx, double *e, double *J, double *lid_e, double *lid_J);
 int sqlm_pose_get_last_step(sqlm_ctx *ctx, int prob, double *H, double *b, double *dx);
 
+/* LiDAR association: the kd-tree search of g2oOptimizer.cc:978-1073 / :560-630 as an exact
+ * brute-force 1-NN on the device.
+ * World transform (pcl::transformPointCloud with an Eigen::Affine3d whose entries are the
+ * float entries of Twc, :985-1010): per coordinate out = (float)(((m0 x + m1 y) + m2 z) + m3)
+ * in double, no FMA. Distance: FLANN's L2_Simple<float>, d = query - map per coordinate in
+ * float, ((dx dx) + dy dy) + dz dz in float, no FMA. The neighbour is the exact minimum over
+ * the concatenated map (cloud order, then point order); equal float distances resolve to the
+ * lowest global index (the reference's tie order depends on FLANN's traversal and is
+ * unpinned). A query is accepted when (double)d2 < dist_sq_threshold, strictly (:1045).
+ * An empty map gives index -1, distance +inf, point 0 and no pair for every query (the
+ * reference would crash). Non-finite coordinates, and distances that overflow a float, are
+ * undefined behaviour of the search (PCL asserts on them); no memory is touched out of bounds.
+ * Twc is the float 4x4 the caller computed, Converter::toCvMat(estimate).inv(): cv::Mat::inv()
+ * is not restated here. */
+int sqlm_lidar_associate(sqlm_ctx *ctx,
+    int n_map_clouds, const int64_t *map_off /*[n_map_clouds+1]*/,
+    const float *map_xyz /*[n_map][3], each cloud in its own sensor frame*/,
+    const float *map_Twc /*[n_map_clouds][16] row-major, NULL = the clouds are already in the world*/,
+    int64_t n_query, const float *query_xyz /*[n_query][3]*/, const float *query_Twc /*[16]*/,
+    double dist_sq_threshold,
+    int32_t *nn_index /*[n_query] global map index, -1 on an empty map*/,
+    float *nn_sq_dist /*[n_query]*/, float *nn_xyz /*[n_query][3] the world map point*/,
+    uint8_t *accepted /*[n_query]*/, int64_t *n_pairs);   /* any output may be NULL */
+
+/* The same search, then the accepted pairs become the context's EdgeLidarFlatPoint edges on
+ * pose `pose_index` (replacing any set before), exactly as sqlm_set_lidar with the pairs in
+ * query order would: p_cam = the query's sensor-frame xyz, p_world = the transformed float map
+ * point, normal = the query's normal, all widened, information `info` (:1062-1070); n_pairs
+ * out. For the call between pass 2 and pass 3. SQLM_ERR_STATE before sqlm_set_problem;
+ * pose_index out of range or naming a fixed pose is SQLM_ERR_INVALID_ARG. */
+int sqlm_set_lidar_from_clouds(sqlm_ctx *ctx, int32_t pose_index,
+    int n_map_clouds, const int64_t *map_off, const float *map_xyz, const float *map_Twc,
+    int64_t n_query, const float *query_xyz, const float *query_Twc,
+    const float *query_normal /*[n_query][3]*/, double info, double dist_sq_threshold, int64_t *n_pairs);
+
+/* What the context's last association ran (tests and tools; no reference counterpart):
+ * out[0] = n_map, out[1] = n_query, out[2] = map segments searched by separate workgroups
+ * (0: empty map or no query, nothing launched), out[3] = map points per LDS tile T,
+ * out[4] = n_pairs, out[5] = queries per workgroup W, out[6..7] = 0. SQLM_ERR_STATE before
+ * any association. */
+int sqlm_lidar_get_exec_info(sqlm_ctx *ctx, int out[8]);
+
 /* Results (write-back inputs, g2oOptimizer.cc:1167-1189, :306-360). */
 int sqlm_get_poses(sqlm_ctx *ctx, double *pose_q, double *pose_t);
 int sqlm_get_points(sqlm_ctx *ctx, double *pt);

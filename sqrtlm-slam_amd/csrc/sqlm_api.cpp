@@ -215,6 +215,7 @@ struct sqlm_ctx {
   EGSolver *eg = nullptr;
   Sim3Solver *sim3 = nullptr;
   PoseSolver *pose = nullptr;
+  LidarSolver *lidar = nullptr;
   OrbEngine *orb = nullptr;
   // ---- timing ----
   hipEvent_t ev[2 * SQLM_NKERNEL_TIMERS] = {};
@@ -2448,6 +2449,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   if (c->eg) eg_destroy(c->eg);
   if (c->sim3) sim3_destroy(c->sim3);
   if (c->pose) pose_destroy(c->pose);
+  if (c->lidar) lidar_destroy(c->lidar);
   if (c->orb) orb_destroy(c->orb);
   for (auto &b : c->bufs)
     if (b.p) (void)hipFree(b.p);
@@ -2788,6 +2790,70 @@ int sqlm_pose_get_last_step(sqlm_ctx *c, int prob, double *H, double *b, double 
   if (!c || !H || !b || !dx) return SQLM_ERR_INVALID_ARG;
   if (!c->pose) return SQLM_ERR_STATE;
   return pose_get_last_step(c->pose, prob, H, b, dx);
+}
+
+namespace {
+
+void lidar_pack(LidarArgs &a, int n_map_clouds, const int64_t *map_off, const float *map_xyz, const float *map_Twc,
+                int64_t n_query, const float *query_xyz, const float *query_Twc, double thr) {
+  a.n_map_clouds = n_map_clouds; a.map_off = map_off; a.map_xyz = map_xyz; a.map_Twc = map_Twc;
+  a.n_query = n_query; a.query_xyz = query_xyz; a.query_Twc = query_Twc; a.thr = thr;
+}
+
+int lidar_call(sqlm_ctx *c, const LidarArgs &a) {
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  if (!c->lidar && !(c->lidar = lidar_create(c->stream, c->n_cu))) return SQLM_ERR_OOM;
+  return lidar_run(c->lidar, a);
+}
+
+}  // namespace
+
+int sqlm_lidar_associate(sqlm_ctx *c, int n_map_clouds, const int64_t *map_off, const float *map_xyz,
+                         const float *map_Twc, int64_t n_query, const float *query_xyz, const float *query_Twc,
+                         double dist_sq_threshold, int32_t *nn_index, float *nn_sq_dist, float *nn_xyz,
+                         uint8_t *accepted, int64_t *n_pairs) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  LidarArgs a;
+  lidar_pack(a, n_map_clouds, map_off, map_xyz, map_Twc, n_query, query_xyz, query_Twc, dist_sq_threshold);
+  a.nn_index = nn_index; a.nn_sq_dist = nn_sq_dist; a.nn_xyz = nn_xyz; a.accepted = accepted; a.n_pairs = n_pairs;
+  if (!lidar_args_ok(a)) return SQLM_ERR_INVALID_ARG;
+  return lidar_call(c, a);
+}
+
+int sqlm_set_lidar_from_clouds(sqlm_ctx *c, int32_t pose_index, int n_map_clouds, const int64_t *map_off,
+                               const float *map_xyz, const float *map_Twc, int64_t n_query, const float *query_xyz,
+                               const float *query_Twc, const float *query_normal, double info,
+                               double dist_sq_threshold, int64_t *n_pairs) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  if (!c->has_problem) return SQLM_ERR_STATE;
+  if (pose_index < 0 || pose_index >= c->n_pose || c->pose_fixed[pose_index]) return SQLM_ERR_INVALID_ARG;
+  LidarArgs a;
+  lidar_pack(a, n_map_clouds, map_off, map_xyz, map_Twc, n_query, query_xyz, query_Twc, dist_sq_threshold);
+  if (!lidar_args_ok(a) || (n_query > 0 && !query_normal)) return SQLM_ERR_INVALID_ARG;
+  if (int s = lidar_call(c, a)) return s;
+  // the accepted pairs in query order (g2oOptimizer.cc:1045-1070): p_cam the
+  // query in its sensor frame, p_world the transformed float map point
+  const int64_t n = lidar_n_pairs(c->lidar);
+  std::vector<int32_t> pose((size_t)n, pose_index);
+  std::vector<double> pc(3 * (size_t)n), pw(3 * (size_t)n), nm(3 * (size_t)n), w((size_t)n, info);
+  const int32_t *pq = n ? lidar_pair_query(c->lidar) : nullptr;
+  const float *xyz = n ? lidar_nn_xyz(c->lidar) : nullptr;
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t i = pq[k];
+    for (int j = 0; j < 3; ++j) {
+      pc[3 * k + j] = (double)query_xyz[3 * i + j];
+      pw[3 * k + j] = (double)xyz[3 * i + j];
+      nm[3 * k + j] = (double)query_normal[3 * i + j];
+    }
+  }
+  if (n_pairs) *n_pairs = n;
+  return sqlm_set_lidar(c, n, pose.data(), pc.data(), pw.data(), nm.data(), w.data());
+}
+
+int sqlm_lidar_get_exec_info(sqlm_ctx *c, int out[8]) {
+  if (!c || !out) return SQLM_ERR_INVALID_ARG;
+  if (!c->lidar) return SQLM_ERR_STATE;
+  return lidar_get_exec_info(c->lidar, out);
 }
 
 int sqlm_global_ba(sqlm_ctx *c, int iterations, const volatile uint8_t *stop, sqlm_stats *st, int *n_iter) {

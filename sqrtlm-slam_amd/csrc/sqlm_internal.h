@@ -500,6 +500,55 @@ int pose_get_edge_chi2(const PoseSolver *s, double *chi2);
 int pose_get_linearization(const PoseSolver *s, double *e, double *J, double *lid_e, double *lid_J);
 int pose_get_last_step(const PoseSolver *s, int prob, double *H, double *b, double *dx);
 
+// LiDAR association (sqlm_lidar.cpp host, sqlm_lidar.hip kernels): exact
+// brute-force 1-NN; one solver per context, on the context's stream; its
+// buffers are reused.
+constexpr int kLidarBlock = 256;                     // lanes of a search workgroup
+constexpr int kLidarQpl = 2;                         // queries a lane keeps in registers
+constexpr int kLidarW = kLidarBlock * kLidarQpl;     // query tile of a workgroup
+constexpr int kLidarT = 512;                         // map points staged in LDS at a time
+constexpr int kLidarEmitBlock = 1024;
+struct LidarDev {  // device pointers of one association
+  int n_map = 0, n_clouds = 0, n_query = 0;
+  int seg_len = 0, n_seg = 0;                  // map points per segment (a multiple of kLidarT), segments
+  int has_Twc = 0;
+  double thr = 0.0;
+  const float *map_xyz = nullptr, *query_xyz = nullptr;  // [n][3], sensor frame
+  const int64_t *map_off = nullptr;                      // [n_clouds+1]
+  const float *map_Twc = nullptr, *query_Twc = nullptr;  // [n_clouds][16], [16]
+  float4 *map_w = nullptr, *query_w = nullptr;           // world xyz, w unused
+  unsigned long long *best = nullptr;                    // [n_query] (bits of d2) << 32 | index
+  int32_t *nn_index = nullptr;
+  float *nn_sq_dist = nullptr, *nn_xyz = nullptr;
+  uint8_t *accepted = nullptr;
+  int32_t *pair_query = nullptr;  // [n_query] the accepted queries, ascending
+  int32_t *n_pairs = nullptr;
+};
+void launch_lidar(const LidarDev &d, hipStream_t st);
+struct LidarSolver;
+LidarSolver *lidar_create(hipStream_t st, int n_cu);
+void lidar_destroy(LidarSolver *s);
+struct LidarArgs {  // host pointers of one call (see include/sqrtlm.h)
+  int n_map_clouds = 0;
+  const int64_t *map_off = nullptr;
+  const float *map_xyz = nullptr, *map_Twc = nullptr;
+  int64_t n_query = 0;
+  const float *query_xyz = nullptr, *query_Twc = nullptr;
+  double thr = 0.0;
+  int32_t *nn_index = nullptr;
+  float *nn_sq_dist = nullptr, *nn_xyz = nullptr;
+  uint8_t *accepted = nullptr;
+  int64_t *n_pairs = nullptr;
+};
+int lidar_args_ok(const LidarArgs &a);
+int lidar_run(LidarSolver *s, const LidarArgs &a);
+// the last lidar_run's results, valid until the next one: the accepted
+// queries in ascending order and every query's world map point
+int64_t lidar_n_pairs(const LidarSolver *s);
+const int32_t *lidar_pair_query(const LidarSolver *s);
+const float *lidar_nn_xyz(const LidarSolver *s);
+int lidar_get_exec_info(const LidarSolver *s, int out[8]);
+
 // ORB front end (sqlm_orb.hip): one engine per context, on the context's stream.
 struct OrbEngine;
 OrbEngine *orb_create(hipStream_t st);

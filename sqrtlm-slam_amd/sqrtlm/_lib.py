@@ -37,6 +37,14 @@ EXPORTS = [
     "sqlm_sim3_optimize", "sqlm_sim3_get_pair_chi2", "sqlm_sim3_get_linearization", "sqlm_sim3_get_last_step",
     "sqlm_pose_optimize", "sqlm_pose_refine_lidar", "sqlm_pose_get_edge_chi2", "sqlm_pose_get_linearization",
     "sqlm_pose_get_last_step",
+    # int sqlm_lidar_associate(ctx, int n_map_clouds, const int64_t *map_off, const float *map_xyz,
+    #     const float *map_Twc, int64_t n_query, const float *query_xyz, const float *query_Twc,
+    #     double dist_sq_threshold, int32_t *nn_index, float *nn_sq_dist, float *nn_xyz, uint8_t *accepted,
+    #     int64_t *n_pairs)
+    # int sqlm_set_lidar_from_clouds(ctx, int32_t pose_index, <map and query arguments as above>,
+    #     const float *query_normal, double info, double dist_sq_threshold, int64_t *n_pairs)
+    # int sqlm_lidar_get_exec_info(ctx, int out[8])
+    "sqlm_lidar_associate", "sqlm_set_lidar_from_clouds", "sqlm_lidar_get_exec_info",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -134,6 +142,12 @@ def lib() -> C.CDLL:
         L.sqlm_version.restype = C.c_char_p
         L.sqlm_status_string.restype = C.c_char_p
         L.sqlm_kernel_timer_name.restype = C.c_char_p
+        if hasattr(L, "sqlm_lidar_associate"):  # build() reports a missing export by name
+            P = C.c_void_p
+            clouds = [C.c_int, P, P, P, C.c_int64, P, P]  # n_map_clouds, map_off, map_xyz, map_Twc, n_query, query_xyz, query_Twc
+            L.sqlm_lidar_associate.argtypes = [P] + clouds + [C.c_double, P, P, P, P, P]
+            L.sqlm_set_lidar_from_clouds.argtypes = [P, C.c_int32] + clouds + [P, C.c_double, C.c_double, P]
+            L.sqlm_lidar_get_exec_info.argtypes = [P, P]
         _lib = L
     return _lib
 

@@ -392,6 +392,57 @@ class Context:
         return H, b, dx
 
 
+    # ------------------------------------------------------------- LiDAR association
+    @staticmethod
+    def _lidar_in(map_clouds, map_Twc, query_xyz, query_Twc):
+        from . import lidar as _l
+        off, mxyz = _l.pack_clouds(map_clouds)
+        K = off.size - 1
+        mT = None if map_Twc is None else np.ascontiguousarray(map_Twc, np.float32).reshape(K, 16)
+        qxyz = np.ascontiguousarray(query_xyz, np.float32).reshape(-1, 3)
+        qT = np.ascontiguousarray(query_Twc, np.float32).reshape(16)
+        return K, off, mxyz, mT, qxyz, qT
+
+    def lidar_associate(self, map_clouds, map_Twc, query_xyz, query_Twc, dist_sq_threshold: float):
+        """sqlm_lidar_associate: ``map_clouds`` a list of (n_k, 3) float32 clouds,
+        each in its own sensor frame with its float T_wc ``map_Twc[k]`` (None:
+        the clouds are in the world already); the queries likewise. Returns
+        (nn_index (n,), nn_sq_dist (n,), nn_xyz (n, 3), accepted (n,));
+        ``self.lidar_n_pairs`` keeps the number of accepted queries."""
+        K, off, mxyz, mT, qxyz, qT = self._lidar_in(map_clouds, map_Twc, query_xyz, query_Twc)
+        n = qxyz.shape[0]
+        idx, d2 = np.zeros(n, np.int32), np.zeros(n, np.float32)
+        xyz, acc = np.zeros((n, 3), np.float32), np.zeros(n, np.uint8)
+        npairs = C.c_int64(0)
+        check(lib().sqlm_lidar_associate(self._h, K, ptr(off), ptr(mxyz), ptr(mT), n, ptr(qxyz), ptr(qT),
+                                         float(dist_sq_threshold), ptr(idx), ptr(d2), ptr(xyz), ptr(acc),
+                                         C.addressof(npairs)), "sqlm_lidar_associate")
+        self.lidar_n_pairs = npairs.value
+        return idx, d2, xyz, acc
+
+    def set_lidar_from_clouds(self, pose_index: int, map_clouds, map_Twc, query_xyz, query_Twc, query_normal,
+                              info: float, dist_sq_threshold: float) -> int:
+        """sqlm_set_lidar_from_clouds: the search of ``lidar_associate``, then the
+        accepted pairs become the EdgeLidarFlatPoint edges of pose
+        ``pose_index``; returns their number."""
+        K, off, mxyz, mT, qxyz, qT = self._lidar_in(map_clouds, map_Twc, query_xyz, query_Twc)
+        nrm = np.ascontiguousarray(query_normal, np.float32).reshape(qxyz.shape)
+        npairs = C.c_int64(0)
+        check(lib().sqlm_set_lidar_from_clouds(self._h, int(pose_index), K, ptr(off), ptr(mxyz), ptr(mT),
+                                               qxyz.shape[0], ptr(qxyz), ptr(qT), ptr(nrm), float(info),
+                                               float(dist_sq_threshold), C.addressof(npairs)),
+              "sqlm_set_lidar_from_clouds")
+        self.lidar_n_pairs = npairs.value
+        return npairs.value
+
+    def lidar_exec_info(self) -> dict:
+        """What the last association ran (sqlm_lidar_get_exec_info)."""
+        out = (C.c_int * 8)()
+        check(lib().sqlm_lidar_get_exec_info(self._h, out), "sqlm_lidar_get_exec_info")
+        return dict(n_map=out[0], n_query=out[1], segments=out[2], map_tile=out[3], n_pairs=out[4],
+                    query_tile=out[5])
+
+
 def comm_unique_id() -> bytes:
     n = lib().sqlm_comm_id_size()
     buf = C.create_string_buffer(n)
@@ -451,17 +502,63 @@ class Optimizer:
         prob.pt[:] = ctx.points()
 
     @classmethod
-    def LocalBundleAdjustment(cls, prob: BAProblem, stop_flag=None, ctx: Context | None = None) -> LBAResult:
+    def LocalBundleAdjustment(cls, prob: BAProblem, stop_flag=None, ctx: Context | None = None,
+                              lidar=None) -> LBAResult:
         """Local BA on an assembled local window (g2oOptimizer.cc:704-1191).
         ``prob.obs_delta`` carries the pass-1 Huber deltas ((float)sqrt(5.991));
         LiDAR flat edges in ``prob`` join in pass 3. Outlier tags returned are
-        the edges the reference erases (chi2 > 5.991 or depth <= 0)."""
+        the edges the reference erases (chi2 > 5.991 or depth <= 0).
+        With ``lidar`` (a lidar.LidarClouds) the pass-3 edges come from the
+        association at the pass-2 poses instead (:978-1073), on the device."""
         c = cls._context(ctx)
         c.set_problem(prob)
+        if lidar is not None:
+            return cls._local_ba_lidar(c, prob, stop_flag, lidar)
         ran, outl, st = c.local_ba(stop_flag)
         if ran:
             cls._write_back(c, prob)
         return LBAResult(bool(ran), outl, st)
+
+    @staticmethod
+    def _tagged(c: Context, prob: BAProblem) -> np.ndarray:
+        """chi2 > 5.991 (7.815 for a stereo edge) or depth <= 0 (:955-970, :1127-1140)."""
+        th = np.full(prob.n_obs, 5.991)
+        if prob.obs_ur is not None:
+            th[prob.obs_ur >= 0] = 7.815
+        return (c.edge_chi2() > th) | (c.depth_positive() == 0)
+
+    @classmethod
+    def _local_ba_lidar(cls, c: Context, prob: BAProblem, stop, clouds) -> LBAResult:
+        """The schedule of sqlm_local_ba driven pass by pass, as an adapter does
+        (INTEGRATION.md section 4), with the association between passes 2 and 3."""
+        from . import lidar as _l
+
+        def stopped():
+            return stop is not None and bool(np.asarray(stop).reshape(-1)[0])
+        zero = _lib.Stats().as_dict()
+        if stopped():  # :923-928
+            return LBAResult(False, np.zeros(prob.n_obs, np.uint8), [zero, zero, zero])
+        if prob.n_lid:  # edges the problem brought are replaced by the association
+            check(lib().sqlm_set_lidar(c._h, C.c_int64(0), None, None, None, None, None), "sqlm_set_lidar")
+        st = [zero, zero, zero]
+        _, st[0] = c.optimize(0, 5, 0.0, stop)
+        if not stopped():  # :939-975
+            level = c.edge_level()
+            level[cls._tagged(c, prob)] = 1
+            c.set_edge_level(level)
+            c.set_robust(None)
+            _, st[1] = c.optimize(0, 10, 0.0, stop)
+        q, t = c.poses()  # :978-1073 at the pass-2 estimates
+        Twc = [_l.Twc_f32(q[p], t[p]) for p in clouds.pose_index]
+        oth = clouds.others
+        c.set_lidar_from_clouds(int(clouds.pose_index[clouds.current]), [clouds.xyz[k] for k in oth],
+                                np.stack([Twc[k] for k in oth]) if oth else np.zeros((0, 16), np.float32),
+                                clouds.query_xyz, Twc[clouds.current], clouds.query_normal, clouds.weight,
+                                clouds.dist_sq_threshold)
+        _, st[2] = c.optimize(0, 20, 0.0, stop)  # :1113-1114
+        outl = cls._tagged(c, prob).astype(np.uint8)  # :1119-1136
+        cls._write_back(c, prob)
+        return LBAResult(True, outl, st)
 
     @classmethod
     def BundleAdjustment(cls, prob: BAProblem, nIterations: int = 5, stop_flag=None, nLoopKF: int = 0,

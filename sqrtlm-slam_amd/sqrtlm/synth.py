@@ -590,6 +590,12 @@ def make_pose_problem(*args, **kw):
     return make(*args, **kw)
 
 
+def make_lidar_clouds(*args, **kw):
+    """A planar scene (ground plane, two walls) seen from K poses as LiDAR flat clouds: see lidar.make_planar_clouds."""
+    from .lidar import make_planar_clouds as make
+    return make(*args, **kw)
+
+
 # ---- synthetic grey images for the ORB front end (SURVEY.md §8 f3) ----------
 
 def make_scene(w: int, h: int, *, seed: int = 0, n_rect: int = 0, n_disk: int = 0) -> np.ndarray:
