@@ -339,6 +339,18 @@ int sqlm_get_points(sqlm_ctx *ctx, double *pt);
 /* e->chi2() from the last computed error (g2o semantics: may belong to a
  * rejected trial, and level-1 edges keep their pass-1 value). */
 int sqlm_get_edge_chi2(sqlm_ctx *ctx, double *chi2);
+/* The _error of every EdgeLidarFlatPoint edge from the last computed error,
+ * err [n_lid] in the caller's edge order (introspection for tests; no
+ * reference counterpart): (T_cw p_w - p_c) . n at the state of the last trial
+ * whose errors were computed, accepted or not. An edge that was inactive in
+ * the last optimize() (fixed pose, other level) keeps the value of the last
+ * optimize() in which it was active, 0 if there was none since the edges were
+ * set -- what the oracle's lid_err holds (oracle/g2o_ref.c computes the error
+ * of active edges only). Completes a pending device-to-host transfer of the
+ * errors like sqlm_get_edge_chi2; adds no work to a trial.
+ * SQLM_ERR_INVALID_ARG on a NULL argument, SQLM_ERR_STATE before a problem is
+ * set or before an optimize() has run on the current LiDAR edges. */
+int sqlm_get_lidar_error(sqlm_ctx *ctx, double *err);
 /* e->isDepthPositive() evaluated at the current estimate. */
 int sqlm_get_edge_depth_positive(sqlm_ctx *ctx, uint8_t *positive);
 int sqlm_get_edge_level(sqlm_ctx *ctx, uint8_t *level);

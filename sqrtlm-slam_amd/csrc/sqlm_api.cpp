@@ -181,6 +181,7 @@ struct sqlm_ctx {
   // (fetched when an edge chi2 is asked for, or before the next prepare())
   bool err_pending = false;
   bool err_zero = false;  // obs_err is still to be sized and zeroed (a new problem: no error computed yet)
+  bool opt_done = false;  // an optimize() has finished on this problem's current LiDAR edge set (sqlm_get_lidar_error)
   // host plan scratch kept across calls (capacity reused: prepare() allocates
   // and first-touches none of its large arrays after the first call)
   TilePlan tp;
@@ -1923,6 +1924,7 @@ int finish(sqlm_ctx *c) {
       for (int k = 0; k < 3; ++k) c->pt[3 * c->slot_pt[s] + k] = X[4 * s + k];
   });
   c->err_pending = d.nE > 0 || d.nLid > 0;
+  c->opt_done = true;
   return SQLM_OK;
 }
 
@@ -2509,6 +2511,7 @@ int sqlm_set_problem(sqlm_ctx *c, int n_pose, const double *pose_q, const double
   par_assign(c->obs_level, obs_level, (size_t)n_obs);  // null: level 0
   c->err_pending = false;  // sized and zeroed when first read (ensure_host_errors)
   c->err_zero = true;
+  c->opt_done = false;
   c->has_stereo = false;
   c->obs_ur.clear(); c->pose_bf.clear(); c->obs_err3.clear();
   c->n_lid = 0;
@@ -2556,6 +2559,7 @@ int sqlm_set_lidar(sqlm_ctx *c, int64_t n, const int32_t *pose, const double *p_
   c->lid_info.assign(info, info + n);
   c->lid_level.assign(n, 0);
   c->lid_err.assign(n, 0.0);
+  c->opt_done = false;
   return SQLM_OK;
 }
 
@@ -2880,6 +2884,15 @@ int sqlm_get_edge_chi2(sqlm_ctx *c, double *chi2) {
   if (int s = fetch_errors(c)) return s;
   ensure_host_errors(c);
   for (int64_t e = 0; e < c->n_obs; ++e) chi2[e] = edge_chi2(c, e);
+  return SQLM_OK;
+}
+
+int sqlm_get_lidar_error(sqlm_ctx *c, double *err) {
+  if (!c || !err) return SQLM_ERR_INVALID_ARG;
+  if (!c->has_problem || !c->opt_done) return SQLM_ERR_STATE;
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  if (int s = fetch_errors(c)) return s;
+  if (c->n_lid) std::memcpy(err, c->lid_err.data(), (size_t)c->n_lid * sizeof(double));
   return SQLM_OK;
 }
 

@@ -45,6 +45,8 @@ EXPORTS = [
     #     const float *query_normal, double info, double dist_sq_threshold, int64_t *n_pairs)
     # int sqlm_lidar_get_exec_info(ctx, int out[8])
     "sqlm_lidar_associate", "sqlm_set_lidar_from_clouds", "sqlm_lidar_get_exec_info",
+    # int sqlm_get_lidar_error(ctx, double *err /* [n_lid] */)
+    "sqlm_get_lidar_error",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",

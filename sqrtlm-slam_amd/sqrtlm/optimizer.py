@@ -210,6 +210,15 @@ class Context:
         check(lib().sqlm_get_edge_chi2(self._h, ptr(out)), "sqlm_get_edge_chi2")
         return out
 
+    def lidar_error(self, n_lid: int | None = None):
+        """(n_lid,) the last computed error of every LiDAR edge in the caller's
+        edge order (sqlm_get_lidar_error); ``n_lid`` defaults to the problem's
+        (pass the pair count after ``set_lidar_from_clouds``)."""
+        n = self.problem.n_lid if n_lid is None else int(n_lid)
+        out = np.zeros(max(n, 1))
+        check(lib().sqlm_get_lidar_error(self._h, ptr(out)), "sqlm_get_lidar_error")
+        return out[:n]
+
     def depth_positive(self):
         out = np.zeros(self.problem.n_obs, np.uint8)
         check(lib().sqlm_get_edge_depth_positive(self._h, ptr(out)), "sqlm_get_edge_depth_positive")

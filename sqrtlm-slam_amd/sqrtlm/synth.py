@@ -417,12 +417,14 @@ def kitti00_map(seed: int = 4, n_kf: int = 1500, n_lm: int = 100000, revisits=KI
 
 
 def add_lidar_flat(prob: BAProblem, pose: int, n: int, *, seed: int = 0, noise: float = 0.01,
-                   weight: float = 50.0) -> BAProblem:
+                   weight: float = 50.0, append: bool = False) -> BAProblem:
     """Attach ``n`` EdgeLidarFlatPoint unary edges to ``pose`` (the current KF of
     local-BA pass 3, g2oOptimizer.cc:1034-1070): a current-frame point p_c with
     its plane normal n_c and a map point p_w on the same plane, so that
     e = (T_cw p_w - p_c) . n_c is zero at the ground-truth pose up to ``noise``.
-    Information = flat_optimized_weight (cfg/lidar_slam.yaml:58)."""
+    Information = flat_optimized_weight (cfg/lidar_slam.yaml:58).
+    ``append`` keeps the edges the problem already has (edges on several
+    poses: one call per pose, each with its own seed) instead of replacing them."""
     rng = SplitMix64(seed ^ 0x5EED)
     gq, gt = prob.meta["gt_q"][pose], prob.meta["gt_t"][pose]
     R = quat_to_mat(gq)[0]
@@ -433,11 +435,11 @@ def add_lidar_flat(prob: BAProblem, pose: int, n: int, *, seed: int = 0, noise: 
     tang -= np.sum(tang * nrm, axis=1, keepdims=True) * nrm
     on_plane = pc + tang + noise * rng.normal(n)[:, None] * nrm
     pw = (on_plane - gt) @ R  # R^T (p - t)
-    prob.lid_pose = np.full(n, pose, np.int32)
-    prob.lid_pc = pc.astype(np.float32).astype(np.float64)
-    prob.lid_pw = pw.astype(np.float32).astype(np.float64)
-    prob.lid_n = nrm.astype(np.float32).astype(np.float64)
-    prob.lid_info = np.full(n, weight)
+    new = dict(lid_pose=np.full(n, pose, np.int32), lid_pc=pc.astype(np.float32).astype(np.float64),
+               lid_pw=pw.astype(np.float32).astype(np.float64), lid_n=nrm.astype(np.float32).astype(np.float64),
+               lid_info=np.full(n, weight))
+    for k, v in new.items():
+        setattr(prob, k, np.concatenate([getattr(prob, k), v]) if append else v)
     prob.validate()
     return prob
 

@@ -25,10 +25,23 @@ Conventions follow the oracle (oracle/g2o_ref.c, oracle/se3_ref.h), i.e. g2o:
 * free cameras are the non-fixed poses with an active edge, in id order
   (hessianIndex), landmarks likewise.
 
-LiDAR edges are NOT handled: their Jacobians are central differences with
-``delta = 1e-9`` (base_unary_edge.hpp:82-122), whose truncation and
-cancellation error an analytic reference does not reproduce. ``first_trial``
-raises on a problem that has any.
+LiDAR edges (EdgeLidarFlatPoint, unary on a pose, no robust kernel) add
+``J^T info J`` to their camera's ``H_pp`` block, ``-J^T info e`` to its ``b_p``
+and ``info e^2`` to the chi2. The error ``e = (q p_w + t - p_c) . n`` is
+evaluated in the reference's number type. The Jacobian is g2o's central
+difference with ``delta = 1e-9`` through oplus (base_unary_edge.hpp:82-122):
+the difference of two errors that agree to ~8 digits, so its value carries
+~1e-7 of cancellation noise that no analytic derivative reproduces. The
+optimizer under test evaluates exactly that float64 expression (the same
+operations in the same order as oracle/g2o_ref.c orc_lidar_jacobian, without
+contraction), so the 1x6 float64 row is taken from the oracle at the float64
+poses and used, cast, in every number type: like the stereo edge's float32
+``invz`` it is part of the problem, not of the arithmetic under test.
+Everything after it (the products with ``info``, the sums into the blocks,
+the Schur complement, the solve) is carried in the reference's number type.
+An edge is active when its level (``prob.meta["lid_level"]``, default 0) is
+the optimised level and its pose is not fixed; an active LiDAR edge makes its
+pose a free camera even without a vision edge at that level.
 
 Everything is vectorised over edges / blocks; a 50-camera, 2000-landmark
 problem takes about a second in longdouble.
@@ -195,9 +208,56 @@ def edges(prob, dtype=LD, pose_q=None, pose_t=None, pt=None, level=0, jac=True) 
     return Edges(eid, p, l, st, r, proj, Jl, Jp, chi2, w, rho)
 
 
+@dataclass
+class LidarEdges:
+    """Active LiDAR edges at a state, in edge-id order."""
+    eid: np.ndarray      # (K,) edge ids
+    pose: np.ndarray     # (K,) pose id
+    e: np.ndarray        # (K,) error
+    J: np.ndarray        # (K,6) the oracle's float64 numeric Jacobian, cast (None without jac)
+    info: np.ndarray     # (K,)
+    chi2: np.ndarray     # (K,) e info e
+
+
+def lidar_level(prob):
+    lv = prob.meta.get("lid_level")
+    return np.zeros(prob.n_lid, np.uint8) if lv is None else np.asarray(lv, np.uint8).reshape(prob.n_lid)
+
+
+def lidar_jacobians(prob, eid, pose_q=None, pose_t=None):
+    """(K,6) float64: orc_lidar_jacobian per edge at float64 poses."""
+    from oracle import oracle as O
+    pose_q = prob.pose_q if pose_q is None else np.asarray(pose_q, np.float64)
+    pose_t = prob.pose_t if pose_t is None else np.asarray(pose_t, np.float64)
+    J = np.zeros((len(eid), 6))
+    for k, e in enumerate(eid):
+        p = prob.lid_pose[e]
+        J[k] = O.lidar_jacobian(pose_q[p], pose_t[p], prob.lid_pc[e], prob.lid_pw[e], prob.lid_n[e])
+    return J
+
+
+def lidar_edges(prob, dtype=LD, pose_q=None, pose_t=None, level=0, jac=True) -> LidarEdges:
+    T = dtype
+    pose_q = prob.pose_q if pose_q is None else np.asarray(pose_q, np.float64)
+    pose_t = prob.pose_t if pose_t is None else np.asarray(pose_t, np.float64)
+    eid = np.nonzero((lidar_level(prob) == level) & (prob.pose_fixed[prob.lid_pose] == 0))[0]
+    p = prob.lid_pose[eid].astype(np.int64)
+    q, t = pose_q[p].astype(T), pose_t[p].astype(T)
+    # orc_lidar_error: se3_map(p_w) - p_c, then (d0 n0 + d1 n1) + d2 n2
+    d = (_rotate(q, prob.lid_pw[eid].astype(T)) + t) - prob.lid_pc[eid].astype(T)
+    n = prob.lid_n[eid].astype(T)
+    e = (d[:, 0] * n[:, 0] + d[:, 1] * n[:, 1]) + d[:, 2] * n[:, 2]
+    info = prob.lid_info[eid].astype(T)
+    J = lidar_jacobians(prob, eid, pose_q, pose_t).astype(T) if jac else None
+    return LidarEdges(eid, p, e, J, info, e * (info * e))
+
+
 def chi2(prob, pose_q=None, pose_t=None, pt=None, dtype=LD, level=0):
     """Total robust chi2 (activeRobustChi2) of the level's edges at a state."""
-    return edges(prob, dtype, pose_q, pose_t, pt, level, jac=False).rho.sum()
+    out = edges(prob, dtype, pose_q, pose_t, pt, level, jac=False).rho.sum()
+    if prob.n_lid:
+        out = out + lidar_edges(prob, dtype, pose_q, pose_t, level, jac=False).chi2.sum()
+    return out
 
 
 # ------------------------------------------------------------------ one trial
@@ -240,13 +300,14 @@ def _solve_refined(S, g):
 
 
 def first_trial(prob, lam, dtype=LD, level=0) -> Trial:
-    if prob.n_lid:
-        raise ValueError("lin_ref has no LiDAR edges (numeric Jacobians)")
     T = dtype
     ed = edges(prob, T, level=level)
+    lid = lidar_edges(prob, T, level=level) if prob.n_lid else None
     lam = T(lam)
     act_pose = np.zeros(prob.n_pose, bool)
     act_pose[ed.pose] = True
+    if lid is not None:
+        act_pose[lid.pose] = True
     free = np.nonzero(act_pose & (prob.pose_fixed == 0))[0]
     act_pt = np.zeros(prob.n_pt, bool)
     act_pt[ed.pt] = True
@@ -271,6 +332,14 @@ def first_trial(prob, lam, dtype=LD, level=0) -> Trial:
     Jp = ed.Jp[fe]
     Hpp = _segsum(np.einsum("eki,ekj->eij", ed.w[fe, None, None] * Jp, Jp), ph, nP)
     bp = _segsum(-np.einsum("eki,ek->ei", Jp, wr[fe]), ph, nP)
+    chi2_0 = ed.rho.sum()
+    if lid is not None and lid.eid.size:
+        # unary edges (BaseUnaryEdge::constructQuadraticForm): every active one is on a free camera
+        Ji = lid.J * lid.info[:, None]
+        lh_ = phid[lid.pose]
+        Hpp = Hpp + _segsum(Ji[:, :, None] * lid.J[:, None, :], lh_, nP)
+        bp = bp - _segsum(Ji * lid.e[:, None], lh_, nP)
+        chi2_0 = chi2_0 + lid.chi2.sum()
     Hpp[:, range(6), range(6)] += lam
 
     # H_pl blocks, one per (landmark, free camera): repeated observations add up
@@ -313,7 +382,7 @@ def first_trial(prob, lam, dtype=LD, level=0) -> Trial:
     dl_act = np.einsum("lij,lj->li", Dinv, cl_)
     dl = np.zeros((prob.n_pt, 3), T)
     dl[lms] = dl_act
-    return Trial(free, lms, Hpp, bp, Hll, bl, S, g, dx, dl, ed.rho.sum(), steps)
+    return Trial(free, lms, Hpp, bp, Hll, bl, S, g, dx, dl, chi2_0, steps)
 
 
 # ------------------------------------------------------------------ rounding spread

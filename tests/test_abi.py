@@ -57,6 +57,7 @@ def test_null_and_invalid_arguments():
     assert L.sqlm_optimize(None, 0, 1, C.c_double(0), None, None, None) == -1
     buf = (C.c_double * 6)()
     assert L.sqlm_get_last_step(None, buf, buf) == -1
+    assert L.sqlm_get_lidar_error(None, buf) == -1
     assert L.sqlm_eg_get_last_step(None, buf, buf) == -1
     out = (C.c_int * 8)()
     assert L.sqlm_eg_get_exec_info(None, out) == -1

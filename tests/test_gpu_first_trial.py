@@ -48,6 +48,7 @@ import functools
 import numpy as np
 import pytest
 
+import lidar_first_trial_cases as lidc
 import lin_ref
 from first_trial_cases import CASES
 
@@ -83,28 +84,45 @@ EXPECT = {
 CLASS_CASES = ("cls3", "cls4", "cls6", "cls8", "cls9")
 
 
+# the harness also runs the LiDAR cases of tests/test_gpu_first_trial_lidar.py
+ALL_CASES = {**CASES, **lidc.CASES}
+
+
+def _level(name):
+    return lidc.LEVEL.get(name, 0)
+
+
 @functools.lru_cache(maxsize=None)
 def _problem(name):
-    return CASES[name][0]()
+    return ALL_CASES[name][0]()
 
 
 @functools.lru_cache(maxsize=None)
 def _reference(name):
     """(spreads, longdouble trial, float64 trial) of the case: computed once."""
-    return lin_ref.spreads(_problem(name), CASES[name][1])
+    return lin_ref.spreads(_problem(name), ALL_CASES[name][1], level=_level(name))
+
+
+def run_problem(ctx, prob, lam, setenv, env, level=0, set_lidar=None):
+    """One trial of `prob` on the GPU; setenv(key, value or None). set_lidar(ctx)
+    replaces the problem's own LiDAR edges after set_problem."""
+    for k in SWITCHES:
+        setenv(k, env.get(k))
+    ctx.set_problem(prob)
+    if set_lidar is not None:
+        set_lidar(ctx)
+    elif prob.meta.get("lid_level") is not None:
+        ctx.set_lidar_level(prob.meta["lid_level"])
+    n, st = ctx.optimize(level, 1, user_lambda=lam)
+    g, dx = ctx.last_step()
+    q, t = ctx.poses()
+    return dict(n=n, st=st, g=g, dx=dx, q=q, t=t, X=ctx.points(), info=ctx.exec_info(), lay=ctx.rcs_layout())
 
 
 def run_gpu(ctx, name, setenv, extra_env=None):
     """One trial of case `name` on the GPU; setenv(key, value or None)."""
-    prob = _problem(name)
-    env = {**CASES[name][2], **(extra_env or {})}
-    for k in SWITCHES:
-        setenv(k, env.get(k))
-    ctx.set_problem(prob)
-    n, st = ctx.optimize(0, 1, user_lambda=CASES[name][1])
-    g, dx = ctx.last_step()
-    q, t = ctx.poses()
-    return dict(n=n, st=st, g=g, dx=dx, q=q, t=t, X=ctx.points(), info=ctx.exec_info(), lay=ctx.rcs_layout())
+    return run_problem(ctx, _problem(name), ALL_CASES[name][1], setenv, {**ALL_CASES[name][2], **(extra_env or {})},
+                       _level(name))
 
 
 def _maxrel(a, b):
@@ -115,6 +133,7 @@ def _maxrel(a, b):
 def ratios(oracle, name, run):
     """GPU error / reference spread per quantity (and both, for the table)."""
     prob = _problem(name)
+    level = _level(name)
     sp, ref, f64 = _reference(name)
     out = {}
 
@@ -124,10 +143,13 @@ def ratios(oracle, name, run):
     put("g", _maxrel(run["g"].reshape(-1), ref.g), sp["g"])
     put("dx", _maxrel(run["dx"].reshape(-1), ref.dx), sp["dx"])
     # points: X0 + dl, the float64 sum's rounding is part of the spread
-    dmax = np.abs(ref.dl).max()
-    X_hi = prob.pt.astype(lin_ref.LD) + ref.dl
-    X_lo = prob.pt + f64.dl
-    put("dl", float(np.abs(run["X"] - X_hi).max() / dmax), float(np.abs(X_lo - X_hi).max() / dmax))
+    if ref.lms.size:
+        dmax = np.abs(ref.dl).max()
+        X_hi = prob.pt.astype(lin_ref.LD) + ref.dl
+        X_lo = prob.pt + f64.dl
+        put("dl", float(np.abs(run["X"] - X_hi).max() / dmax), float(np.abs(X_lo - X_hi).max() / dmax))
+    else:  # no active landmark (a level with LiDAR edges only): no point may move
+        put("dl", float(np.abs(run["X"] - prob.pt).max()), 0.0)
     # poses: oplus(initial, dx) in the oracle's float64 SE3Quat arithmetic
     q_hi, t_hi = lin_ref.oplus_poses(oracle, prob, ref.free, ref.dx.astype(np.float64))
     q_lo, t_lo = lin_ref.oplus_poses(oracle, prob, f64.free, f64.dx)
@@ -135,7 +157,7 @@ def ratios(oracle, name, run):
     put("pose", max(np.abs(run["q"] - q_hi).max(), np.abs(run["t"] - t_hi).max() / ts),
         max(np.abs(q_lo - q_hi).max(), np.abs(t_lo - t_hi).max() / ts))
     # trial chi2 at the state the GPU returned
-    chi_hi, chi_sp = lin_ref.chi2_spread(prob, run["q"], run["t"], run["X"])
+    chi_hi, chi_sp = lin_ref.chi2_spread(prob, run["q"], run["t"], run["X"], level)
     put("chi2", float(abs(lin_ref.LD(run["st"]["trace_chi2"][0]) - chi_hi) / chi_hi), chi_sp)
     return out
 

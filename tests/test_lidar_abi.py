@@ -67,6 +67,22 @@ def test_invalid_arguments_without_a_device():
     assert _from_clouds(L, None, 0, 1, off, f, f, 2, f, f, None) == -1
 
 
+def test_lidar_error_getter_at_every_layer():
+    """sqlm_get_lidar_error: declared among the result getters, bound, exported,
+    wrapped; without a context it answers INVALID_ARG whatever the buffer."""
+    from sqrtlm.optimizer import Context
+    hdr = open(os.path.join(ROOT, "include", "sqrtlm.h")).read()
+    assert re.search(r"\bint\s+sqlm_get_lidar_error\s*\(\s*sqlm_ctx\s*\*\s*ctx\s*,\s*double\s*\*\s*err\s*\)\s*;", hdr)
+    assert hdr.index("int sqlm_get_edge_chi2(") < hdr.index("int sqlm_get_lidar_error(") < hdr.index("int sqlm_get_rcs_layout(")
+    assert "sqlm_get_lidar_error" in _lib.EXPORTS
+    L = _lib.lib()
+    assert hasattr(L, "sqlm_get_lidar_error") and callable(Context.lidar_error)
+    buf = np.zeros(4)
+    assert L.sqlm_get_lidar_error(None, _lib.ptr(buf)) == -1
+    assert L.sqlm_get_lidar_error(None, None) == -1
+    assert not buf.any()
+
+
 def test_python_facade():
     import inspect
 
