@@ -245,11 +245,6 @@ struct sqlm_ctx {
   int kernel_ms_n = 0;
 };
 
-#define HIP_OK(x)                          \
-  do {                                     \
-    if ((x) != hipSuccess) return SQLM_ERR_HIP; \
-  } while (0)
-
 namespace {
 
 template <class T>
@@ -273,7 +268,7 @@ template <class T>
 int upload(sqlm_ctx *c, int idx, const std::vector<T> &v, T **out) {
   int s = ensure(c, idx, v.size(), out);
   if (s) return s;
-  if (!v.empty()) HIP_OK(hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  if (!v.empty()) SQLM_HIP_OK(hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
   return SQLM_OK;
 }
 
@@ -336,7 +331,7 @@ template <class T>
 int upload(sqlm_ctx *c, int idx, const PinVec<T> &v, T **out) {
   int s = ensure(c, idx, v.size(), out);
   if (s) return s;
-  if (v.size()) HIP_OK(hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
+  if (v.size()) SQLM_HIP_OK(hipMemcpyAsync(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c->stream));
   return SQLM_OK;
 }
 
@@ -933,7 +928,7 @@ int prepare(sqlm_ctx *c, int level) {
   c->step_valid = false;
   // the page-locked staging arrays are rewritten (or regrown) below: no DMA of
   // an earlier call, finished or abandoned on an error path, may still read them
-  HIP_OK(hipStreamSynchronize(c->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   // SQLM_PREP_TIMING=1: host phase times of this setup on stderr
   const bool ptime = std::getenv("SQLM_PREP_TIMING") != nullptr;
   auto pt0 = std::chrono::steady_clock::now();
@@ -1609,7 +1604,7 @@ int prepare(sqlm_ctx *c, int level) {
   UP(B_HIDXP, hidxp, d.hidx_pose);
   UP(B_X0, X, d.X[0]);
   AL(B_X1, 4 * (size_t)nL, d.X[1]);
-  if (nL) HIP_OK(hipMemcpyAsync(d.X[1], d.X[0], 4 * (size_t)nL * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  if (nL) SQLM_HIP_OK(hipMemcpyAsync(d.X[1], d.X[0], 4 * (size_t)nL * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   UP(B_LMBEG, lm_begin, d.lm_begin);
   AL(B_LMR, 8 * (size_t)nL, d.lm_R);
   AL(B_LMB, 4 * (size_t)nL, d.lm_b);
@@ -1749,7 +1744,7 @@ int prepare(sqlm_ctx *c, int level) {
     {  // completion words of the one-launch back substitution, from epoch 0
       int *dn = nullptr;
       AL(B_CRDONE, (size_t)c->cr.p, dn);
-      HIP_OK(hipMemsetAsync(dn, 0, (size_t)c->cr.p * sizeof(int), c->stream));
+      SQLM_HIP_OK(hipMemsetAsync(dn, 0, (size_t)c->cr.p * sizeof(int), c->stream));
       c->crs = CRSync{dn, c->cr.p, 0};
     }
     if (c->cr.R) {  // band + border layout
@@ -1784,7 +1779,7 @@ int prepare(sqlm_ctx *c, int level) {
   AL(B_SCAL, (size_t)kNScalars, d.scalars);
   AL(B_MAXD, 1, d.maxdiag);
   AL(B_FLAGS, 4, d.flags);
-  HIP_OK(hipMemsetAsync(d.flags, 0, 4 * sizeof(int), c->stream));  // flags[1]: sticky device error of the solves
+  SQLM_HIP_OK(hipMemsetAsync(d.flags, 0, 4 * sizeof(int), c->stream));  // flags[1]: sticky device error of the solves
   d.hdiag = nullptr;
   d.xstage = nullptr;
   if (c->comm.enabled()) {
@@ -1830,16 +1825,16 @@ int prepare(sqlm_ctx *c, int level) {
     PinVec<uint8_t> stg;
     if ((st = pinned(c, P_ARENA, small.host.size(), stg))) return st;
     std::memcpy(stg.data(), small.host.data(), small.host.size());
-    HIP_OK(hipMemcpyAsync(dev, stg.data(), small.host.size(), hipMemcpyHostToDevice, c->stream));
+    SQLM_HIP_OK(hipMemcpyAsync(dev, stg.data(), small.host.size(), hipMemcpyHostToDevice, c->stream));
     for (const auto &[off, p] : small.dst) *p = dev + off;
   }
 #undef UP
 #undef UPD
 #undef AL
-  HIP_OK(hipMemsetAsync(d.partials, 0, sizeof(double) * kMaxPartials, c->stream));
-  HIP_OK(hipMemsetAsync(d.maxdiag, 0, sizeof(unsigned long long), c->stream));
-  HIP_OK(hipMemsetAsync(d.obs_err, 0, sizeof(double) * 2 * std::max<int64_t>(nE, 1), c->stream));
-  if (d.obs_err3) HIP_OK(hipMemsetAsync(d.obs_err3, 0, sizeof(double) * std::max<int64_t>(nE, 1), c->stream));
+  SQLM_HIP_OK(hipMemsetAsync(d.partials, 0, sizeof(double) * kMaxPartials, c->stream));
+  SQLM_HIP_OK(hipMemsetAsync(d.maxdiag, 0, sizeof(unsigned long long), c->stream));
+  SQLM_HIP_OK(hipMemsetAsync(d.obs_err, 0, sizeof(double) * 2 * std::max<int64_t>(nE, 1), c->stream));
+  if (d.obs_err3) SQLM_HIP_OK(hipMemsetAsync(d.obs_err3, 0, sizeof(double) * std::max<int64_t>(nE, 1), c->stream));
   launch_pose_prep(d, 0, c->stream);
   phase("upload");
   if (ptime) {  // how long the queued copies and setup kernels still run after the host is done
@@ -1879,11 +1874,11 @@ int fetch_errors(sqlm_ctx *c) {
   stage(P_RERR3, d.obs_err3 ? (size_t)d.nE : 0, err3, 1);
   stage(P_RLERR, (size_t)d.nLid, lerr, 2);
   if (err3.size())
-    HIP_OK(hipMemcpyAsync(err3.data(), d.obs_err3, err3.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (d.nE) HIP_OK(hipMemcpyAsync(err.data(), d.obs_err, err.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    SQLM_HIP_OK(hipMemcpyAsync(err3.data(), d.obs_err3, err3.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (d.nE) SQLM_HIP_OK(hipMemcpyAsync(err.data(), d.obs_err, err.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (d.nLid)
-    HIP_OK(hipMemcpyAsync(lerr.data(), d.lid_err, lerr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
+    SQLM_HIP_OK(hipMemcpyAsync(lerr.data(), d.lid_err, lerr.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   const int nth = host_threads(d.nE);
   run_threads(nth, [&](int t) {
     for (int64_t o = d.nE * t / nth; o < d.nE * (t + 1) / nth; ++o) {
@@ -1911,9 +1906,9 @@ int finish(sqlm_ctx *c) {
   };
   stage(P_RQT, 8 * (size_t)c->n_pose, qt, 0);
   stage(P_RX, 4 * (size_t)d.nL, X, 1);
-  HIP_OK(hipMemcpyAsync(qt.data(), d.pose_qt[0], qt.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  if (d.nL) HIP_OK(hipMemcpyAsync(X.data(), d.X[0], X.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
+  SQLM_HIP_OK(hipMemcpyAsync(qt.data(), d.pose_qt[0], qt.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (d.nL) SQLM_HIP_OK(hipMemcpyAsync(X.data(), d.X[0], X.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   for (int p = 0; p < c->n_pose; ++p) {
     for (int k = 0; k < 4; ++k) c->pose_q[4 * p + k] = qt[8 * p + k];
     for (int k = 0; k < 3; ++k) c->pose_t[3 * p + k] = qt[8 * p + 4 + k];
@@ -1953,16 +1948,16 @@ int linearize(sqlm_ctx *c) {
   c->lin_timers = 2;  // + the camera pass on the side stream
   // the camera pass (H_pp, b_p, LiDAR) reads only the state, like the landmark
   // QR: fork it onto the side stream and join before anything consumes H_pp
-  HIP_OK(hipEventRecord(c->ev_fork, c->stream));
-  HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
-  if (c->timing) HIP_OK(hipEventRecord(c->ev[2], c->side));
+  SQLM_HIP_OK(hipEventRecord(c->ev_fork, c->stream));
+  SQLM_HIP_OK(hipStreamWaitEvent(c->side, c->ev_fork, 0));
+  if (c->timing) SQLM_HIP_OK(hipEventRecord(c->ev[2], c->side));
   launch_camera_pass(d, c->side);
-  if (c->timing) HIP_OK(hipEventRecord(c->ev[3], c->side));
-  HIP_OK(hipEventRecord(c->ev_join, c->side));
+  if (c->timing) SQLM_HIP_OK(hipEventRecord(c->ev[3], c->side));
+  SQLM_HIP_OK(hipEventRecord(c->ev_join, c->side));
   tmark(c, 0, false);  // maxdiag was zeroed by the last k_reduce (or prepare)
   for (size_t b = 0; b < c->buckets.size(); ++b) launch_linearize(d, c->buckets[b], c->bucket_part_off[b], c->stream);
   tmark(c, 0, true);
-  HIP_OK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+  SQLM_HIP_OK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
   if (c->comm.enabled() && c->need_maxdiag) {  // lambda_0 needs the summed pose diagonals
     launch_pose_diag(d, c->stream);
     if (comm_allreduce_dev(c->comm, d.hdiag, 6 * (int64_t)d.nP, SQLM_DT_F64, SQLM_OP_SUM, c->stream))
@@ -2011,9 +2006,9 @@ int spec_camera_pass(sqlm_ctx *c, hipStream_t st) {
       c->kernel_ms_acc[1] += ms;
     c->cam_pending[p] = false;
   }
-  if (c->timing) HIP_OK(hipEventRecord(c->ev_cam[p][0], st));
+  if (c->timing) SQLM_HIP_OK(hipEventRecord(c->ev_cam[p][0], st));
   launch_camera_pass(c->d, st, true);
-  if (c->timing) { HIP_OK(hipEventRecord(c->ev_cam[p][1], st)); c->cam_pending[p] = true; }
+  if (c->timing) { SQLM_HIP_OK(hipEventRecord(c->ev_cam[p][1], st)); c->cam_pending[p] = true; }
   c->cam_par ^= 1;
   return SQLM_OK;
 }
@@ -2023,12 +2018,12 @@ int spec_camera_pass(sqlm_ctx *c, hipStream_t st) {
 // before the next trial's RCS reduce.
 int spec_camera_launch(sqlm_ctx *c) {
   if (!c->cam_inline) {
-    HIP_OK(hipEventRecord(c->ev_spec_fork, c->stream));
-    HIP_OK(hipStreamWaitEvent(c->side, c->ev_spec_fork, 0));
+    SQLM_HIP_OK(hipEventRecord(c->ev_spec_fork, c->stream));
+    SQLM_HIP_OK(hipStreamWaitEvent(c->side, c->ev_spec_fork, 0));
   }
   if (int s = spec_camera_pass(c, c->cam_inline ? c->stream : c->side)) return s;
   if (!c->cam_inline) {
-    HIP_OK(hipEventRecord(c->ev_spec_join, c->side));
+    SQLM_HIP_OK(hipEventRecord(c->ev_spec_join, c->side));
     c->spec_outstanding = true;
   }
   return SQLM_OK;
@@ -2053,8 +2048,8 @@ int reduce_and_fetch(sqlm_ctx *c, TrialOut &o, bool cam_after = false) {
     if (s) return s;
   }
   if (!h) {
-    HIP_OK(hipMemcpyAsync(c->h_scalars, d.scalars, sizeof(double) * kNScalars, hipMemcpyDeviceToHost, c->stream));
-    HIP_OK(hipStreamSynchronize(c->stream));
+    SQLM_HIP_OK(hipMemcpyAsync(c->h_scalars, d.scalars, sizeof(double) * kNScalars, hipMemcpyDeviceToHost, c->stream));
+    SQLM_HIP_OK(hipStreamSynchronize(c->stream));
     h = c->h_scalars;
   }
   o.chi_cur = h[kChiCur];
@@ -2091,7 +2086,7 @@ int trial_launch(sqlm_ctx *c, double lambda, bool &cam_after) {
   hmark(c, 1);  // damp + tile launches
   tmark(c, 8, false);
   if (c->spec_outstanding) {  // H_pp / b_p (if swapped in) and the trial state buffers it reads
-    HIP_OK(hipStreamWaitEvent(c->stream, c->ev_spec_join, 0));
+    SQLM_HIP_OK(hipStreamWaitEvent(c->stream, c->ev_spec_join, 0));
     c->spec_outstanding = false;
   }
   if (c->use_tiles) {
@@ -2099,8 +2094,8 @@ int trial_launch(sqlm_ctx *c, double lambda, bool &cam_after) {
     // kernel cleared them (no memset launches) unless there were no tiles
     if (d.cr_direct && d.n_tiles == 0) {
       const size_t blkbytes = (size_t)c->cr.p * c->cr.n * c->cr.n * sizeof(double);
-      HIP_OK(hipMemsetAsync(d.cr_D, 0, blkbytes, c->stream));
-      HIP_OK(hipMemsetAsync(d.cr_E, 0, blkbytes, c->stream));
+      SQLM_HIP_OK(hipMemsetAsync(d.cr_D, 0, blkbytes, c->stream));
+      SQLM_HIP_OK(hipMemsetAsync(d.cr_E, 0, blkbytes, c->stream));
     }
     if (d.cr_direct && c->cr.R) launch_arrow_clear(d, c->cr, c->stream);
     launch_rcs_reduce(d, lambda, c->stream);
@@ -2279,7 +2274,7 @@ int run_lm(sqlm_ctx *c, int iterations, double user_lambda, const volatile uint8
     st->ms_trials += tr.ms();
   }
   if (c->spec_outstanding) {  // nothing of a speculative pass outlives the run
-    HIP_OK(hipStreamWaitEvent(c->stream, c->ev_spec_join, 0));
+    SQLM_HIP_OK(hipStreamWaitEvent(c->stream, c->ev_spec_join, 0));
     c->spec_outstanding = false;
   }
   flush_cam_timers(c);
@@ -2688,8 +2683,13 @@ int sqlm_sim3_optimize(sqlm_ctx *c, int n_prob, const double *S12, const double 
     return SQLM_ERR_INVALID_ARG;
   if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
   if (!c->sim3 && !(c->sim3 = sim3_create(c->stream))) return SQLM_ERR_OOM;
-  return sim3_optimize(c->sim3, n_prob, S12, intr1, intr2, fix_scale, th2, pair_off, X1c, X2c, obs1, obs2, info1, info2,
-                       iters, user_lambda, S12_out, n_inliers, pair_state, stats);
+  Sim3Args a;
+  a.n_prob = n_prob;
+  a.S12 = S12; a.intr1 = intr1; a.intr2 = intr2; a.fix_scale = fix_scale; a.th2 = th2; a.pair_off = pair_off;
+  a.X1c = X1c; a.X2c = X2c; a.obs1 = obs1; a.obs2 = obs2; a.info1 = info1; a.info2 = info2;
+  a.iters = iters; a.user_lambda = user_lambda;
+  a.S12_out = S12_out; a.n_inliers = n_inliers; a.pair_state = pair_state; a.stats = stats;
+  return sim3_optimize(c->sim3, a);
 }
 
 int sqlm_sim3_get_pair_chi2(sqlm_ctx *c, double *chi2) {
@@ -2949,9 +2949,9 @@ int sqlm_get_last_step(sqlm_ctx *c, double *g, double *dx) {
   // g: rcs_put_g / k_rcs; dx: the dense solve's copy, or on a CR layout the
   // pose update's copy of the CR / border solution. Nothing after the trial
   // (speculative camera pass, finish) writes either.
-  HIP_OK(hipMemcpyAsync(g, c->d.g, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipMemcpyAsync(dx, c->d.dx, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-  HIP_OK(hipStreamSynchronize(c->stream));
+  SQLM_HIP_OK(hipMemcpyAsync(g, c->d.g, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SQLM_HIP_OK(hipMemcpyAsync(dx, c->d.dx, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   return SQLM_OK;
 }
 
@@ -3094,7 +3094,7 @@ int sqlm_bench_iterations(sqlm_ctx *c, int warmup, int n, double *ms_per_iter, d
     s = prepare(c, 0);
     if (s) return s;
   }
-  HIP_OK(hipStreamSynchronize(c->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   s = comm_barrier(c->comm, c->stream);
   if (s) return s;
   c->timing = kernel_ms != nullptr;
@@ -3102,7 +3102,7 @@ int sqlm_bench_iterations(sqlm_ctx *c, int warmup, int n, double *ms_per_iter, d
   c->kernel_ms_n = 0;
   Timer t;
   s = run_lm(c, n, 0.0, nullptr, st, nullptr, true);
-  HIP_OK(hipStreamSynchronize(c->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   const double ms = t.ms();
   c->timing = false;
   if (s) return s;

@@ -12,6 +12,12 @@
 
 namespace sqlm {
 
+// a failed HIP call ends the enclosing function with SQLM_ERR_HIP
+#define SQLM_HIP_OK(x)                          \
+  do {                                          \
+    if ((x) != hipSuccess) return SQLM_ERR_HIP; \
+  } while (0)
+
 #ifndef SQLM_TILE_MAXCAMS
 #define SQLM_TILE_MAXCAMS 24
 #endif
@@ -440,11 +446,21 @@ void launch_sim3(const Sim3Dev &d, hipStream_t st);
 struct Sim3Solver;
 Sim3Solver *sim3_create(hipStream_t st);
 void sim3_destroy(Sim3Solver *s);
-int sim3_optimize(Sim3Solver *s, int n_prob, const double *S12, const double *intr1, const double *intr2,
-                  const uint8_t *fix_scale, const double *th2, const int64_t *pair_off, const double *X1c,
-                  const double *X2c, const double *obs1, const double *obs2, const double *info1, const double *info2,
-                  const int32_t iters[3], double user_lambda, double *S12_out, int32_t *n_inliers, uint8_t *pair_state,
-                  struct sqlm_sim3_stats *stats);
+struct Sim3Args {  // host pointers of one call (see include/sqrtlm.h)
+  int n_prob = 0;
+  const double *S12 = nullptr, *intr1 = nullptr, *intr2 = nullptr;
+  const uint8_t *fix_scale = nullptr;
+  const double *th2 = nullptr;
+  const int64_t *pair_off = nullptr;
+  const double *X1c = nullptr, *X2c = nullptr, *obs1 = nullptr, *obs2 = nullptr, *info1 = nullptr, *info2 = nullptr;
+  const int32_t *iters = nullptr;  // [3], null: Sim3Dev's defaults
+  double user_lambda = 0.0;
+  double *S12_out = nullptr;
+  int32_t *n_inliers = nullptr;
+  uint8_t *pair_state = nullptr;
+  struct sqlm_sim3_stats *stats = nullptr;
+};
+int sim3_optimize(Sim3Solver *s, const Sim3Args &a);
 int sim3_get_pair_chi2(const Sim3Solver *s, double *chi2);
 int sim3_get_linearization(const Sim3Solver *s, double *e, double *J);
 int sim3_get_last_step(const Sim3Solver *s, int prob, double *H, double *b, double *dx);

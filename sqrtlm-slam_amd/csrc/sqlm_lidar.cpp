@@ -8,33 +8,20 @@
 #include <new>
 
 #include "sqlm_internal.h"
+#include "sqlm_staging.h"
 
 namespace sqlm {
-
-#define LS_HIP(x)                              \
-  do {                                         \
-    if ((x) != hipSuccess) return SQLM_ERR_HIP; \
-  } while (0)
 
 struct LidarSolver {
   hipStream_t stream = nullptr;
   int n_cu = 256;
   // input arena, work arena (world clouds, best words) and output arena on the
   // device; pinned mirrors of the input and the output
-  char *d_in = nullptr, *d_work = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-  size_t cap_in = 0, cap_work = 0, cap_out = 0;
+  Staged in, work, out;
   bool ran = false;
   int64_t n_map = 0, n_query = 0, n_pairs = 0;
   int n_seg = 0;
-  size_t o_xyz = 0, o_pq = 0;  // offsets into h_out of the last call
-
-  ~LidarSolver() {
-    if (d_in) (void)hipFree(d_in);
-    if (d_work) (void)hipFree(d_work);
-    if (d_out) (void)hipFree(d_out);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-  }
+  size_t o_xyz = 0, o_pq = 0;  // offsets into out.host of the last call
 };
 
 LidarSolver *lidar_create(hipStream_t st, int n_cu) {
@@ -47,35 +34,6 @@ LidarSolver *lidar_create(hipStream_t st, int n_cu) {
 }
 
 void lidar_destroy(LidarSolver *s) { delete s; }
-
-namespace {
-
-// host == nullptr: device memory only
-int grow(char **dev, char **host, size_t *cap, size_t need) {
-  if (need <= *cap) return SQLM_OK;
-  if (*dev) (void)hipFree(*dev);
-  if (host && *host) (void)hipHostFree(*host);
-  *dev = nullptr;
-  if (host) *host = nullptr;
-  *cap = 0;
-  const size_t n = need + need / 2;
-  if (hipMalloc((void **)dev, n) != hipSuccess) return SQLM_ERR_OOM;
-  if (host && hipHostMalloc((void **)host, n, hipHostMallocDefault) != hipSuccess) return SQLM_ERR_OOM;
-  *cap = n;
-  return SQLM_OK;
-}
-
-// bump allocation in 16-byte steps
-struct Arena {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return o;
-  }
-};
-
-}  // namespace
 
 int lidar_args_ok(const LidarArgs &a) {
   if (a.n_map_clouds < 0 || a.n_query < 0 || !a.map_off) return 0;
@@ -120,18 +78,18 @@ int lidar_run(LidarSolver *s, const LidarArgs &a) {
   const size_t o_idx = out.take(nqs * sizeof(int32_t)), o_d2 = out.take(nqs * sizeof(float)),
                o_xyz = out.take(3 * nqs * sizeof(float)), o_acc = out.take(nqs), o_pq = out.take(nqs * sizeof(int32_t)),
                o_np = out.take(sizeof(int32_t));
-  if (int r = grow(&s->d_in, &s->h_in, &s->cap_in, in.off)) return r;
-  if (int r = grow(&s->d_work, nullptr, &s->cap_work, work.off)) return r;
-  if (int r = grow(&s->d_out, &s->h_out, &s->cap_out, out.off)) return r;
+  if (int r = s->in.grow(in.off)) return r;
+  if (int r = s->work.grow(work.off, false)) return r;  // device only
+  if (int r = s->out.grow(out.off)) return r;
 
-  char *h = s->h_in;
+  char *h = s->in.host;
   std::memcpy(h + i_map, a.map_xyz + 3 * b, 3 * nm * sizeof(float));
-  int64_t *off = reinterpret_cast<int64_t *>(h + i_off);
+  int64_t *off = at<int64_t>(h, i_off);
   for (size_t c = 0; c <= nc; ++c) off[c] = a.map_off[c] - b;
   if (a.map_Twc) std::memcpy(h + i_Twc, a.map_Twc, 16 * nc * sizeof(float));
   std::memcpy(h + i_q, a.query_xyz, 3 * nqs * sizeof(float));
   std::memcpy(h + i_qT, a.query_Twc, 16 * sizeof(float));
-  LS_HIP(hipMemcpyAsync(s->d_in, s->h_in, in.off, hipMemcpyHostToDevice, s->stream));
+  SQLM_HIP_OK(hipMemcpyAsync(s->in.dev, s->in.host, in.off, hipMemcpyHostToDevice, s->stream));
 
   // Map segments: enough workgroups to cover every CU about twice, no segment
   // shorter than four LDS tiles; SQLM_LIDAR_SPLIT=s forces s (an A/B switch:
@@ -156,27 +114,27 @@ int lidar_run(LidarSolver *s, const LidarArgs &a) {
   d.n_seg = (int)((n_tiles + seg_tiles - 1) / seg_tiles);
   d.has_Twc = a.map_Twc != nullptr;
   d.thr = a.thr;
-  d.map_xyz = reinterpret_cast<const float *>(s->d_in + i_map);
-  d.map_off = reinterpret_cast<const int64_t *>(s->d_in + i_off);
-  d.map_Twc = reinterpret_cast<const float *>(s->d_in + i_Twc);
-  d.query_xyz = reinterpret_cast<const float *>(s->d_in + i_q);
-  d.query_Twc = reinterpret_cast<const float *>(s->d_in + i_qT);
-  d.map_w = reinterpret_cast<float4 *>(s->d_work + w_map);
-  d.query_w = reinterpret_cast<float4 *>(s->d_work + w_q);
-  d.best = reinterpret_cast<unsigned long long *>(s->d_work + w_best);
-  d.nn_index = reinterpret_cast<int32_t *>(s->d_out + o_idx);
-  d.nn_sq_dist = reinterpret_cast<float *>(s->d_out + o_d2);
-  d.nn_xyz = reinterpret_cast<float *>(s->d_out + o_xyz);
-  d.accepted = reinterpret_cast<uint8_t *>(s->d_out + o_acc);
-  d.pair_query = reinterpret_cast<int32_t *>(s->d_out + o_pq);
-  d.n_pairs = reinterpret_cast<int32_t *>(s->d_out + o_np);
+  d.map_xyz = at<const float>(s->in.dev, i_map);
+  d.map_off = at<const int64_t>(s->in.dev, i_off);
+  d.map_Twc = at<const float>(s->in.dev, i_Twc);
+  d.query_xyz = at<const float>(s->in.dev, i_q);
+  d.query_Twc = at<const float>(s->in.dev, i_qT);
+  d.map_w = at<float4>(s->work.dev, w_map);
+  d.query_w = at<float4>(s->work.dev, w_q);
+  d.best = at<unsigned long long>(s->work.dev, w_best);
+  d.nn_index = at<int32_t>(s->out.dev, o_idx);
+  d.nn_sq_dist = at<float>(s->out.dev, o_d2);
+  d.nn_xyz = at<float>(s->out.dev, o_xyz);
+  d.accepted = at<uint8_t>(s->out.dev, o_acc);
+  d.pair_query = at<int32_t>(s->out.dev, o_pq);
+  d.n_pairs = at<int32_t>(s->out.dev, o_np);
   launch_lidar(d, s->stream);
-  LS_HIP(hipGetLastError());
-  LS_HIP(hipMemcpyAsync(s->h_out, s->d_out, out.off, hipMemcpyDeviceToHost, s->stream));
-  LS_HIP(hipStreamSynchronize(s->stream));
+  SQLM_HIP_OK(hipGetLastError());
+  SQLM_HIP_OK(hipMemcpyAsync(s->out.host, s->out.dev, out.off, hipMemcpyDeviceToHost, s->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(s->stream));
 
-  const char *ho = s->h_out;
-  s->n_pairs = *reinterpret_cast<const int32_t *>(ho + o_np);
+  char *ho = s->out.host;
+  s->n_pairs = *at<const int32_t>(ho, o_np);
   if (a.nn_index) std::memcpy(a.nn_index, ho + o_idx, nqs * sizeof(int32_t));
   if (a.nn_sq_dist) std::memcpy(a.nn_sq_dist, ho + o_d2, nqs * sizeof(float));
   if (a.nn_xyz) std::memcpy(a.nn_xyz, ho + o_xyz, 3 * nqs * sizeof(float));
@@ -192,8 +150,8 @@ int lidar_run(LidarSolver *s, const LidarArgs &a) {
 }
 
 int64_t lidar_n_pairs(const LidarSolver *s) { return s->ran ? s->n_pairs : 0; }
-const int32_t *lidar_pair_query(const LidarSolver *s) { return reinterpret_cast<const int32_t *>(s->h_out + s->o_pq); }
-const float *lidar_nn_xyz(const LidarSolver *s) { return reinterpret_cast<const float *>(s->h_out + s->o_xyz); }
+const int32_t *lidar_pair_query(const LidarSolver *s) { return at<const int32_t>(s->out.host, s->o_pq); }
+const float *lidar_nn_xyz(const LidarSolver *s) { return at<const float>(s->out.host, s->o_xyz); }
 
 int lidar_get_exec_info(const LidarSolver *s, int out[8]) {
   if (!s->ran) return SQLM_ERR_STATE;

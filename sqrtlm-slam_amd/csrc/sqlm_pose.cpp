@@ -6,30 +6,17 @@
 #include <new>
 
 #include "sqlm_internal.h"
+#include "sqlm_staging.h"
 
 namespace sqlm {
 
-#define PS_HIP(x)                              \
-  do {                                         \
-    if ((x) != hipSuccess) return SQLM_ERR_HIP; \
-  } while (0)
-
 struct PoseSolver {
   hipStream_t stream = nullptr;
-  // one input arena and one output arena on the device, one pinned mirror of each
-  char *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
-  size_t cap_in = 0, cap_out = 0;
+  Staged in, out;    // one input and one output arena on the device, a pinned mirror of each
   bool ran = false;  // a call has completed: the introspection below is valid
   int n_prob = 0;
   int64_t n_obs = 0, n_lid = 0;
-  size_t o_chi2 = 0, o_line = 0, o_linJ = 0, o_lide = 0, o_lidJ = 0, o_step = 0;  // offsets into h_out of the last call
-
-  ~PoseSolver() {
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-  }
+  size_t o_chi2 = 0, o_line = 0, o_linJ = 0, o_lide = 0, o_lidJ = 0, o_step = 0;  // offsets into out.host of the last call
 };
 
 PoseSolver *pose_create(hipStream_t st) {
@@ -39,33 +26,6 @@ PoseSolver *pose_create(hipStream_t st) {
 }
 
 void pose_destroy(PoseSolver *s) { delete s; }
-
-namespace {
-
-int grow(char **dev, char **host, size_t *cap, size_t need) {
-  if (need <= *cap) return SQLM_OK;
-  if (*dev) (void)hipFree(*dev);
-  if (*host) (void)hipHostFree(*host);
-  *dev = *host = nullptr;
-  *cap = 0;
-  const size_t n = need + need / 2;
-  if (hipMalloc((void **)dev, n) != hipSuccess) return SQLM_ERR_OOM;
-  if (hipHostMalloc((void **)host, n, hipHostMallocDefault) != hipSuccess) return SQLM_ERR_OOM;
-  *cap = n;
-  return SQLM_OK;
-}
-
-// bump allocation in 16-byte steps
-struct Arena {
-  size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off += (bytes + 15) & ~(size_t)15;
-    return o;
-  }
-};
-
-}  // namespace
 
 int pose_run(PoseSolver *s, const PoseArgs &a) {
   const int n_prob = a.n_prob;
@@ -88,18 +48,18 @@ int pose_run(PoseSolver *s, const PoseArgs &a) {
                o_chi2 = out.take(kPoseChecks * nq * D), o_line = out.take(2 * nq * D), o_linJ = out.take(12 * nq * D),
                o_lide = out.take(nl * D), o_lidJ = out.take(6 * nl * D), o_step = out.take(kPoseStepLen * np * D);
   s->ran = false;
-  if (int r = grow(&s->d_in, &s->h_in, &s->cap_in, in.off)) return r;
-  if (int r = grow(&s->d_out, &s->h_out, &s->cap_out, out.off)) return r;
+  if (int r = s->in.grow(in.off)) return r;
+  if (int r = s->out.grow(out.off)) return r;
 
-  char *h = s->h_in;
-  double *hp = reinterpret_cast<double *>(h + i_pose);
+  char *h = s->in.host;
+  double *hp = at<double>(h, i_pose);
   for (size_t k = 0; k < np; ++k) {
     for (int c = 0; c < 4; ++c) hp[8 * k + c] = a.pose_q[4 * k + c];
     for (int c = 0; c < 3; ++c) hp[8 * k + 4 + c] = a.pose_t[3 * k + c];
     hp[8 * k + 7] = 0.0;
   }
   std::memcpy(h + i_k, a.intr, 4 * np * D);
-  int64_t *off = reinterpret_cast<int64_t *>(h + i_off), *loff = reinterpret_cast<int64_t *>(h + i_loff);
+  int64_t *off = at<int64_t>(h, i_off), *loff = at<int64_t>(h, i_loff);
   for (size_t k = 0; k <= np; ++k) {
     off[k] = a.obs_off[k] - b;
     loff[k] = a.refine ? a.lid_off[k] - lb : 0;
@@ -118,8 +78,8 @@ int pose_run(PoseSolver *s, const PoseArgs &a) {
     std::memcpy(h + i_n, a.lid_n + 3 * lb, 3 * nl * D);
     std::memcpy(h + i_lw, a.lid_info + lb, nl * D);
   }
-  PS_HIP(hipMemcpyAsync(s->d_in, s->h_in, in.off, hipMemcpyHostToDevice, s->stream));
-  PS_HIP(hipMemsetAsync(s->d_out, 0, out.off, s->stream));
+  SQLM_HIP_OK(hipMemcpyAsync(s->in.dev, s->in.host, in.off, hipMemcpyHostToDevice, s->stream));
+  SQLM_HIP_OK(hipMemsetAsync(s->out.dev, 0, out.off, s->stream));
 
   PoseDev d;
   d.n_prob = n_prob;
@@ -127,28 +87,27 @@ int pose_run(PoseSolver *s, const PoseArgs &a) {
   for (int k = 0; k < 5; ++k) d.iters[k] = a.iters[k];
   d.user_lambda = a.user_lambda;
   d.th2 = a.th2;
-  const char *di = s->d_in;
-  char *dout = s->d_out;
-  auto cd = [&](size_t o) { return reinterpret_cast<const double *>(di + o); };
-  auto od = [&](size_t o) { return reinterpret_cast<double *>(dout + o); };
+  char *di = s->in.dev, *dout = s->out.dev;
+  auto cd = [&](size_t o) { return at<const double>(di, o); };
+  auto od = [&](size_t o) { return at<double>(dout, o); };
   d.pose = cd(i_pose);
   d.intr = cd(i_k);
-  d.obs_off = reinterpret_cast<const int64_t *>(di + i_off);
+  d.obs_off = at<const int64_t>(di, i_off);
   d.Xw = cd(i_X);
   d.uv = cd(i_uv);
   d.info = cd(i_w);
-  d.outlier_in = reinterpret_cast<const uint8_t *>(di + i_oin);
-  d.robust_on = reinterpret_cast<const uint8_t *>(di + i_rob);
-  d.lid_off = reinterpret_cast<const int64_t *>(di + i_loff);
-  d.lid_kind = reinterpret_cast<const uint8_t *>(di + i_kind);
+  d.outlier_in = at<const uint8_t>(di, i_oin);
+  d.robust_on = at<const uint8_t>(di, i_rob);
+  d.lid_off = at<const int64_t>(di, i_loff);
+  d.lid_kind = at<const uint8_t>(di, i_kind);
   d.lid_pc = cd(i_pc);
   d.lid_pw = cd(i_pw);
   d.lid_n = cd(i_n);
   d.lid_info = cd(i_lw);
   d.pose_out = od(o_pose);
-  d.n_inliers = reinterpret_cast<int32_t *>(dout + o_nin);
-  d.stats = reinterpret_cast<sqlm_pose_stats *>(dout + o_st);
-  d.outlier = reinterpret_cast<uint8_t *>(dout + o_flag);
+  d.n_inliers = at<int32_t>(dout, o_nin);
+  d.stats = at<sqlm_pose_stats>(dout, o_st);
+  d.outlier = at<uint8_t>(dout, o_flag);
   d.edge_chi2 = od(o_chi2);
   d.lin_e = od(o_line);
   d.lin_J = od(o_linJ);
@@ -156,18 +115,18 @@ int pose_run(PoseSolver *s, const PoseArgs &a) {
   d.lid_J = od(o_lidJ);
   d.last_step = od(o_step);
   launch_pose(d, s->stream);
-  PS_HIP(hipGetLastError());
-  PS_HIP(hipMemcpyAsync(s->h_out, s->d_out, out.off, hipMemcpyDeviceToHost, s->stream));
-  PS_HIP(hipStreamSynchronize(s->stream));
+  SQLM_HIP_OK(hipGetLastError());
+  SQLM_HIP_OK(hipMemcpyAsync(s->out.host, s->out.dev, out.off, hipMemcpyDeviceToHost, s->stream));
+  SQLM_HIP_OK(hipStreamSynchronize(s->stream));
 
-  const double *po = reinterpret_cast<const double *>(s->h_out + o_pose);
+  const double *po = at<const double>(s->out.host, o_pose);
   for (size_t k = 0; k < np; ++k) {
     for (int c = 0; c < 4; ++c) a.pose_q_out[4 * k + c] = po[8 * k + c];
     for (int c = 0; c < 3; ++c) a.pose_t_out[3 * k + c] = po[8 * k + 4 + c];
   }
-  std::memcpy(a.n_inliers, s->h_out + o_nin, np * sizeof(int32_t));
-  if (nq) std::memcpy(a.outlier + b, s->h_out + o_flag, nq);
-  if (a.stats) std::memcpy(a.stats, s->h_out + o_st, np * sizeof(sqlm_pose_stats));
+  std::memcpy(a.n_inliers, s->out.host + o_nin, np * sizeof(int32_t));
+  if (nq) std::memcpy(a.outlier + b, s->out.host + o_flag, nq);
+  if (a.stats) std::memcpy(a.stats, s->out.host + o_st, np * sizeof(sqlm_pose_stats));
   s->n_prob = n_prob;
   s->n_obs = n_obs;
   s->n_lid = n_lid;
@@ -183,24 +142,24 @@ int pose_run(PoseSolver *s, const PoseArgs &a) {
 
 int pose_get_edge_chi2(const PoseSolver *s, double *chi2) {
   if (!s->ran) return SQLM_ERR_STATE;
-  if (s->n_obs) std::memcpy(chi2, s->h_out + s->o_chi2, kPoseChecks * (size_t)s->n_obs * sizeof(double));
+  if (s->n_obs) std::memcpy(chi2, s->out.host + s->o_chi2, kPoseChecks * (size_t)s->n_obs * sizeof(double));
   return SQLM_OK;
 }
 
 int pose_get_linearization(const PoseSolver *s, double *e, double *J, double *lid_e, double *lid_J) {
   if (!s->ran) return SQLM_ERR_STATE;
   const size_t nq = (size_t)s->n_obs, nl = (size_t)s->n_lid, D = sizeof(double);
-  if (e && nq) std::memcpy(e, s->h_out + s->o_line, 2 * nq * D);
-  if (J && nq) std::memcpy(J, s->h_out + s->o_linJ, 12 * nq * D);
-  if (lid_e && nl) std::memcpy(lid_e, s->h_out + s->o_lide, nl * D);
-  if (lid_J && nl) std::memcpy(lid_J, s->h_out + s->o_lidJ, 6 * nl * D);
+  if (e && nq) std::memcpy(e, s->out.host + s->o_line, 2 * nq * D);
+  if (J && nq) std::memcpy(J, s->out.host + s->o_linJ, 12 * nq * D);
+  if (lid_e && nl) std::memcpy(lid_e, s->out.host + s->o_lide, nl * D);
+  if (lid_J && nl) std::memcpy(lid_J, s->out.host + s->o_lidJ, 6 * nl * D);
   return SQLM_OK;
 }
 
 int pose_get_last_step(const PoseSolver *s, int prob, double *H, double *b, double *dx) {
   if (!s->ran) return SQLM_ERR_STATE;
   if (prob < 0 || prob >= s->n_prob) return SQLM_ERR_INVALID_ARG;
-  const double *o = reinterpret_cast<const double *>(s->h_out + s->o_step) + kPoseStepLen * (size_t)prob;
+  const double *o = at<const double>(s->out.host, s->o_step) + kPoseStepLen * (size_t)prob;
   if (o[49] == 0.0) return SQLM_ERR_STATE;  // the problem ran no trial
   std::memcpy(H, o, 36 * sizeof(double));
   std::memcpy(b, o + 36, 6 * sizeof(double));

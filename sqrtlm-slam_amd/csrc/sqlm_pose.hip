@@ -18,6 +18,7 @@
 #include "../../include/sqrtlm.h"
 #include "se3_dev.h"
 #include "sqlm_internal.h"
+#include "sqlm_small_lm.h"
 
 namespace sqlm {
 
@@ -40,27 +41,6 @@ struct PShared {
   LMCtl L;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// Sum over the workgroup, waves added in wave order; every thread gets it.
-__device__ double block_sum(PShared &sh, double v) {
-  v = wave_sum(v);
-  __syncthreads();  // the previous use of red / bsum is over
-  if ((threadIdx.x & 63) == 0) sh.red[threadIdx.x >> 6][0] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = sh.red[0][0];
-    for (int w = 1; w < kPWaves; ++w) r += sh.red[w][0];
-    sh.bsum = r;
-  }
-  __syncthreads();
-  return sh.bsum;
-}
-
 struct PProb {
   int64_t o0, l0;  // first mono edge, first LiDAR edge
   int np, nl;
@@ -68,20 +48,6 @@ struct PProb {
   float th2f;
   double K[4];
 };
-
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho, rho'; no
-// kernel: rho = chi2, rho' = 1
-__device__ __forceinline__ void robustify(double chi, bool robust, double delta, double dsqr, double &rho0,
-                                          double &rho1) {
-  if (!robust || chi <= dsqr) {
-    rho0 = chi;
-    rho1 = 1.0;
-  } else {
-    const double sq = sqrt(chi);
-    rho0 = 2 * sq * delta - dsqr;
-    rho1 = delta / sq;
-  }
-}
 
 // plain chi2 of mono edge g at the pose A
 __device__ __forceinline__ double mono_chi2(const PoseDev &d, const PProb &pb, const double *A, int64_t g) {
@@ -143,7 +109,7 @@ __device__ void linearize(PShared &sh, const PoseDev &d, const PProb &pb, bool r
     }
     if (!act) continue;
     double rho0, rho1;
-    robustify(e[0] * (w * e[0]) + e[1] * (w * e[1]), robust, pb.delta, pb.dsqr, rho0, rho1);
+    huber(e[0] * (w * e[0]) + e[1] * (w * e[1]), robust, pb.delta, pb.dsqr, rho0, rho1);
     const double ww = rho1 * w;                                    // weightedOmega = rho' Omega
     const double r0 = -(w * e[0]) * rho1, r1 = -(w * e[1]) * rho1;  // omega_r * rho'
     int k = 0;
@@ -184,19 +150,7 @@ __device__ void linearize(PShared &sh, const PoseDev &d, const PProb &pb, bool r
       acc[27] += e * (w * e);
     }
   }
-#pragma unroll
-  for (int k = 0; k < kPAcc; ++k) acc[k] = wave_sum(acc[k]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kPAcc; ++k) sh.red[threadIdx.x >> 6][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kPAcc) {
-    double r = sh.red[0][threadIdx.x];
-    for (int w = 1; w < kPWaves; ++w) r += sh.red[w][threadIdx.x];
-    sh.Hb[threadIdx.x] = r;
-  }
-  __syncthreads();
+  reduce_acc<kPAcc, kPWaves>(sh, acc);
 }
 
 // activeRobustChi2 at the pose A over the same edges.
@@ -210,7 +164,7 @@ __device__ double robust_chi2(PShared &sh, const PoseDev &d, const PProb &pb, co
     const int64_t g = pb.o0 + i;
     if (d.outlier[g]) continue;
     double rho0, rho1;
-    robustify(mono_chi2(d, pb, A, g), robust, pb.delta, pb.dsqr, rho0, rho1);
+    huber(mono_chi2(d, pb, A, g), robust, pb.delta, pb.dsqr, rho0, rho1);
     chi += rho0;
   }
   if (lidar)
@@ -219,58 +173,7 @@ __device__ double robust_chi2(PShared &sh, const PoseDev &d, const PProb &pb, co
       const double e = lidar_err(d, A, g);
       chi += e * (d.lid_info[g] * e);
     }
-  return block_sum(sh, chi);
-}
-
-// (H + lambda I) dx = b by Cholesky (LinearSolverDense, linear_solver_dense.h:
-// 100-118: a non-positive pivot is a failed solve, the step is rejected).
-// Hb: packed upper triangle (21), b (6).
-__device__ bool solve6(const double *Hb, double lambda, double dx[6]) {
-  double A[6][6];
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = i; j < 6; ++j) A[j][i] = Hb[k++];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) A[i][i] += lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 6; ++j) {
-    double dj = A[j][j];
-#pragma unroll
-    for (int c = 0; c < j; ++c) dj -= A[j][c] * A[j][c];
-    if (!(dj > 0.0)) ok = false;
-    dj = sqrt(dj);
-    A[j][j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < 6; ++i) {
-      double s = A[i][j];
-#pragma unroll
-      for (int c = 0; c < j; ++c) s -= A[i][c] * A[j][c];
-      A[i][j] = s / dj;
-    }
-  }
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-    double s = Hb[21 + i];
-#pragma unroll
-    for (int c = 0; c < i; ++c) s -= A[i][c] * y[c];
-    y[i] = s / A[i][i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int c = i + 1; c < 6; ++c) s -= A[c][i] * dx[c];
-    dx[i] = s / A[i][i];
-  }
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dx[i] = 0.0;
-  }
-  return ok;
+  return block_sum<kPWaves>(sh, chi);
 }
 
 // initializeOptimization(0); optimize(niter) on the level-0 edges
@@ -282,13 +185,11 @@ __device__ bool run_stage(PShared &sh, const PoseDev &d, const PProb &pb, int st
                           bool lidar, bool write, sqlm_pose_stats *st) {
   double na = 0.0;
   for (int i = threadIdx.x; i < pb.np; i += kPBlock) na += d.outlier[pb.o0 + i] == 0 ? 1.0 : 0.0;
-  const int n_act = (int)block_sum(sh, na) + (lidar ? pb.nl : 0);
+  const int n_act = (int)block_sum<kPWaves>(sh, na) + (lidar ? pb.nl : 0);
   const bool run = niter > 0 && n_act > 0;
   LMCtl &L = sh.L;
   if (threadIdx.x == 0) {
-    L.lambda = 0.0; L.ni = 2.0; L.currentChi = 0.0; L.iniChi = 0.0; L.chi2_end = 0.0; L.lambda_end = 0.0;
-    L.qmax = 0; L.nbad = 0; L.its = 0; L.result = 0; L.trials = 0; L.iterations = niter; L.bench = 0;
-    L.done = !run;
+    lm_reset(L, niter, !run);
     st->active[stage] = n_act;
   }
   __syncthreads();
@@ -302,18 +203,14 @@ __device__ bool run_stage(PShared &sh, const PoseDev &d, const PProb &pb, int st
     if (threadIdx.x == 0 && it == 0) {  // levenberg.cpp:66-97 at iteration 0
       L.currentChi = L.iniChi = sh.Hb[27];
       st->chi2_begin[stage] = sh.Hb[27];
-      double md = 0.0;  // computeLambdaInit
-      int k = 0;
-      for (int i = 0; i < 6; ++i) { md = fmax(fabs(sh.Hb[k]), md); k += 6 - i; }
-      L.lambda = d.user_lambda > 0 ? d.user_lambda : 1e-5 * md;
+      L.lambda = lm_lambda_init<6>(sh.Hb, d.user_lambda);
       L.ni = 2;
     }
     for (int q = 0; q < 10; ++q) {
       if (threadIdx.x == 0) {
         double dx[6], t[8];
-        const bool ok = solve6(sh.Hb, L.lambda, dx);
-        double scale = 0.0;  // computeScale
-        for (int j = 0; j < 6; ++j) scale += dx[j] * (L.lambda * dx[j] + sh.Hb[21 + j]);
+        const bool ok = chol_solve<6>(sh.Hb, L.lambda, dx);
+        const double scale = lm_scale<6>(sh.Hb, dx, L.lambda);
         for (int k = 0; k < 8; ++k) t[k] = sh.S[k];
         se3_oplus(t, t + 4, dx);
         for (int k = 0; k < 8; ++k) { sh.T[k] = t[k]; sh.E[k] = t[k]; }
@@ -337,11 +234,7 @@ __device__ bool run_stage(PShared &sh, const PoseDev &d, const PProb &pb, int st
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    st->iterations[stage] = L.its;
-    st->trials[stage] = L.trials;
-    st->result[stage] = L.result;
-    st->chi2_end[stage] = L.chi2_end;
-    st->lambda_end[stage] = L.lambda_end;
+    lm_store_stage(st, stage, L);
   }
   return true;
 }
@@ -369,7 +262,7 @@ __device__ int check_edges(PShared &sh, const PoseDev &d, const PProb &pb, int c
     d.outlier[g] = out ? 1 : 0;
     bad += out ? 1.0 : 0.0;
   }
-  return (int)block_sum(sh, bad);
+  return (int)block_sum<kPWaves>(sh, bad);
 }
 
 __global__ __launch_bounds__(kPBlock) void k_pose(PoseDev d) {
@@ -433,10 +326,7 @@ __global__ __launch_bounds__(kPBlock) void k_pose(PoseDev d) {
     for (int k = 0; k < 8; ++k) d.pose_out[8 * prob + k] = sh.S[k];
     if (sh.have_step) {  // sqlm_pose_get_last_step
       double *o = d.last_step + kPoseStepLen * (int64_t)prob;
-      int k = 0;
-      for (int i = 0; i < 6; ++i)
-        for (int j = i; j < 6; ++j) { o[6 * i + j] = sh.Hb[k]; o[6 * j + i] = sh.Hb[k]; ++k; }
-      for (int j = 0; j < 6; ++j) { o[36 + j] = sh.Hb[21 + j]; o[42 + j] = sh.dx[j]; }
+      store_last_step<6>(o, sh.Hb, sh.dx);
       o[48] = sh.lambda;
       o[49] = 1.0;
     }

@@ -21,6 +21,7 @@
 #include "../../include/sqrtlm.h"
 #include "sim3_dev.h"
 #include "sqlm_internal.h"
+#include "sqlm_small_lm.h"
 
 namespace sqlm {
 
@@ -43,27 +44,6 @@ struct S3Shared {
   LMCtl L;
 };
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// Sum over the workgroup, waves added in wave order; every thread gets it.
-__device__ double block_sum(S3Shared &sh, double v) {
-  v = wave_sum(v);
-  __syncthreads();  // the previous use of red / bsum is over
-  if ((threadIdx.x & 63) == 0) sh.red[threadIdx.x >> 6][0] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = sh.red[0][0];
-    for (int w = 1; w < kS3Waves; ++w) r += sh.red[w][0];
-    sh.bsum = r;
-  }
-  __syncthreads();
-  return sh.bsum;
-}
-
 struct S3Prob {
   int64_t p0;
   int np;
@@ -73,18 +53,6 @@ struct S3Prob {
 };
 
 __device__ __forceinline__ double edge_chi2(const double e[2], double w) { return e[0] * (w * e[0]) + e[1] * (w * e[1]); }
-
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho, rho'
-__device__ __forceinline__ void huber(double chi, double delta, double dsqr, double &rho0, double &rho1) {
-  if (chi <= dsqr) {
-    rho0 = chi;
-    rho1 = 1.0;
-  } else {
-    const double sq = sqrt(chi);
-    rho0 = 2 * sq * delta - dsqr;
-    rho1 = delta / sq;
-  }
-}
 
 // The 14 perturbed estimates of the central differences and all inverses:
 // they do not depend on the edge, so they are computed once per linearization.
@@ -141,7 +109,7 @@ __device__ void linearize(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, bool
           for (int c = 0; c < 7; ++c) d.lin_J[28 * g + 14 * side + 7 * r + c] = J[r][c];
       }
       double rho0, rho1;
-      huber(edge_chi2(e, w), pb.delta, pb.dsqr, rho0, rho1);
+      huber(edge_chi2(e, w), true, pb.delta, pb.dsqr, rho0, rho1);
       const double ww = rho1 * w;                                    // weightedOmega = rho' Omega
       const double r0 = -(w * e[0]) * rho1, r1 = -(w * e[1]) * rho1;  // omega_r * rho'
       int k = 0;
@@ -156,19 +124,7 @@ __device__ void linearize(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, bool
       acc[35] += rho0;
     }
   }
-#pragma unroll
-  for (int k = 0; k < kS3Acc; ++k) acc[k] = wave_sum(acc[k]);
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < kS3Acc; ++k) sh.red[threadIdx.x >> 6][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < kS3Acc) {
-    double r = sh.red[0][threadIdx.x];
-    for (int w = 1; w < kS3Waves; ++w) r += sh.red[w][threadIdx.x];
-    sh.Hb[threadIdx.x] = r;
-  }
-  __syncthreads();
+  reduce_acc<kS3Acc, kS3Waves>(sh, acc);
 }
 
 // activeRobustChi2 at the Sim3 (A, Ai) over the active pairs.
@@ -182,63 +138,13 @@ __device__ double robust_chi2(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, 
     const double o1[2] = {d.obs1[2 * g], d.obs1[2 * g + 1]}, o2[2] = {d.obs2[2 * g], d.obs2[2 * g + 1]};
     double e[2], rho0, rho1;
     sim3_project_error(A, X2, pb.K1, o1, e);
-    huber(edge_chi2(e, d.info1[g]), pb.delta, pb.dsqr, rho0, rho1);
+    huber(edge_chi2(e, d.info1[g]), true, pb.delta, pb.dsqr, rho0, rho1);
     chi += rho0;
     sim3_project_error(Ai, X1, pb.K2, o2, e);
-    huber(edge_chi2(e, d.info2[g]), pb.delta, pb.dsqr, rho0, rho1);
+    huber(edge_chi2(e, d.info2[g]), true, pb.delta, pb.dsqr, rho0, rho1);
     chi += rho0;
   }
-  return block_sum(sh, chi);
-}
-
-// (H + lambda I) dx = b by Cholesky (LinearSolverDense: a non-positive pivot
-// is a failed solve, the step is rejected). Hb: packed upper triangle, b.
-__device__ bool solve7(const double *Hb, double lambda, double dx[7]) {
-  double A[7][7];
-  int k = 0;
-#pragma unroll
-  for (int i = 0; i < 7; ++i)
-#pragma unroll
-    for (int j = i; j < 7; ++j) A[j][i] = Hb[k++];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) A[i][i] += lambda;
-  bool ok = true;
-#pragma unroll
-  for (int j = 0; j < 7; ++j) {
-    double dj = A[j][j];
-#pragma unroll
-    for (int c = 0; c < j; ++c) dj -= A[j][c] * A[j][c];
-    if (!(dj > 0.0)) ok = false;
-    dj = sqrt(dj);
-    A[j][j] = dj;
-#pragma unroll
-    for (int i = j + 1; i < 7; ++i) {
-      double s = A[i][j];
-#pragma unroll
-      for (int c = 0; c < j; ++c) s -= A[i][c] * A[j][c];
-      A[i][j] = s / dj;
-    }
-  }
-  double y[7];
-#pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    double s = Hb[28 + i];
-#pragma unroll
-    for (int c = 0; c < i; ++c) s -= A[i][c] * y[c];
-    y[i] = s / A[i][i];
-  }
-#pragma unroll
-  for (int i = 6; i >= 0; --i) {
-    double s = y[i];
-#pragma unroll
-    for (int c = i + 1; c < 7; ++c) s -= A[c][i] * dx[c];
-    dx[i] = s / A[i][i];
-  }
-  if (!ok) {
-#pragma unroll
-    for (int i = 0; i < 7; ++i) dx[i] = 0.0;
-  }
-  return ok;
+  return block_sum<kS3Waves>(sh, chi);
 }
 
 // initializeOptimization(); optimize(niter) on the active pairs
@@ -246,11 +152,7 @@ __device__ bool solve7(const double *Hb, double lambda, double dx[7]) {
 __device__ void run_stage(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, int stage, int niter,
                           sqlm_sim3_stats *st) {
   LMCtl &L = sh.L;
-  if (threadIdx.x == 0) {
-    L.lambda = 0.0; L.ni = 2.0; L.currentChi = 0.0; L.iniChi = 0.0; L.chi2_end = 0.0; L.lambda_end = 0.0;
-    L.qmax = 0; L.nbad = 0; L.its = 0; L.result = 0; L.trials = 0; L.iterations = niter; L.bench = 0;
-    L.done = niter <= 0;
-  }
+  if (threadIdx.x == 0) lm_reset(L, niter, niter <= 0);
   __syncthreads();
   for (int it = 0; it < niter; ++it) {
     if (L.done) break;  // LDS, the same for every thread
@@ -258,18 +160,14 @@ __device__ void run_stage(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, int 
     if (threadIdx.x == 0 && it == 0) {  // levenberg.cpp:66-97 at iteration 0
       L.currentChi = L.iniChi = sh.Hb[35];
       st->chi2_begin[stage] = sh.Hb[35];
-      double md = 0.0;  // computeLambdaInit
-      int k = 0;
-      for (int i = 0; i < 7; ++i) { md = fmax(fabs(sh.Hb[k]), md); k += 7 - i; }
-      L.lambda = d.user_lambda > 0 ? d.user_lambda : 1e-5 * md;
+      L.lambda = lm_lambda_init<7>(sh.Hb, d.user_lambda);
       L.ni = 2;
     }
     for (int q = 0; q < 10; ++q) {
       if (threadIdx.x == 0) {
         double dx[7], t[8], ti[8];
-        const bool ok = solve7(sh.Hb, L.lambda, dx);
-        double scale = 0.0;  // computeScale
-        for (int j = 0; j < 7; ++j) scale += dx[j] * (L.lambda * dx[j] + sh.Hb[28 + j]);
+        const bool ok = chol_solve<7>(sh.Hb, L.lambda, dx);
+        const double scale = lm_scale<7>(sh.Hb, dx, L.lambda);
         for (int k = 0; k < 8; ++k) t[k] = sh.S[k];
         sim3_oplus(t, dx, pb.fix);
         sim3_inverse(t, ti);
@@ -294,11 +192,7 @@ __device__ void run_stage(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, int 
   }
   __syncthreads();
   if (threadIdx.x == 0) {
-    st->iterations[stage] = L.its;
-    st->trials[stage] = L.trials;
-    st->result[stage] = L.result;
-    st->chi2_end[stage] = L.chi2_end;
-    st->lambda_end[stage] = L.lambda_end;
+    lm_store_stage(st, stage, L);
     const int n = L.its < SQLM_SIM3_TRACE_MAX ? L.its : SQLM_SIM3_TRACE_MAX;
     st->trace_len[stage] = n;
     for (int k = 0; k < n; ++k) {
@@ -339,7 +233,7 @@ __device__ int check_pairs(S3Shared &sh, const Sim3Dev &d, const S3Prob &pb, int
       bad += 1.0;
     }
   }
-  return (int)block_sum(sh, bad);
+  return (int)block_sum<kS3Waves>(sh, bad);
 }
 
 __global__ __launch_bounds__(kS3Block) void k_sim3(Sim3Dev d) {
@@ -383,10 +277,7 @@ __global__ __launch_bounds__(kS3Block) void k_sim3(Sim3Dev d) {
   }
   if (threadIdx.x == 0 && sh.have_step) {  // sqlm_sim3_get_last_step
     double *o = d.last_step + 64 * (int64_t)prob;
-    int k = 0;
-    for (int i = 0; i < 7; ++i)
-      for (int j = i; j < 7; ++j) { o[7 * i + j] = sh.Hb[k]; o[7 * j + i] = sh.Hb[k]; ++k; }
-    for (int j = 0; j < 7; ++j) { o[49 + j] = sh.Hb[28 + j]; o[56 + j] = sh.dx[j]; }
+    store_last_step<7>(o, sh.Hb, sh.dx);
     o[63] = 1.0;
   }
 }
