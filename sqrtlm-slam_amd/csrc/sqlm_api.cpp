@@ -181,6 +181,12 @@ struct sqlm_ctx {
   // (fetched when an edge chi2 is asked for, or before the next prepare())
   bool err_pending = false;
   bool err_zero = false;  // obs_err is still to be sized and zeroed (a new problem: no error computed yet)
+  // The state buffer the last error evaluation of this setup used: -1 none yet,
+  // 0 a full linearize(), 1 a trial (an accepted trial's swap_state makes it 0).
+  // fetch_errors evaluates the edge errors there (k_edge_errors); the LM loop
+  // itself stores none unless trial_stores (SQLM_TRIAL_STORES=1, per prepare)
+  int err_state = -1;
+  bool trial_stores = false;
   bool opt_done = false;  // an optimize() has finished on this problem's current LiDAR edge set (sqlm_get_lidar_error)
   // host plan scratch kept across calls (capacity reused: prepare() allocates
   // and first-touches none of its large arrays after the first call)
@@ -1213,7 +1219,8 @@ int prepare(sqlm_ctx *c, int level) {
   const int nth = host_threads(c->n_obs);
   auto par = [&](auto &&fn) { run_threads(nth, fn); };
   std::vector<uint8_t> inexact(nth, 0);
-  auto put = [&](int64_t e, int o, int sl, bool &bad) {
+  // flg: 1 = some input is not a float32 value, 2 = some edge has a robust kernel
+  auto put = [&](int64_t e, int o, int sl, uint8_t &flg) {
     c->dev_edge[o] = e;
     obs_lm[o] = sl;
     obs_cam[o] = c->obs_pose[e];
@@ -1224,7 +1231,8 @@ int prepare(sqlm_ctx *c, int level) {
     obs_q[4 * (size_t)o + 1] = fv;
     obs_q[4 * (size_t)o + 2] = fw;
     obs_q[4 * (size_t)o + 3] = fd;
-    bad |= (double)fu != u || (double)fv != v || (double)fw != w || (double)fd != dl;
+    flg |= ((double)fu != u || (double)fv != v || (double)fw != w || (double)fd != dl) ? 1 : 0;
+    flg |= dl > 0.0 ? 2 : 0;
     if (c->has_stereo) obs_ur[o] = c->obs_ur[e];
   };
   bool contig = c->n_obs <= (int64_t)std::numeric_limits<int>::max();
@@ -1243,7 +1251,7 @@ int prepare(sqlm_ctx *c, int level) {
     // slot order: the outputs are written front to back (whole cache lines)
     // and each landmark's inputs are one run of edge ids
     par([&](int t) {
-      bool bad = false;
+      uint8_t bad = 0;
       const int s1 = (int)((int64_t)nL * (t + 1) / nth);
       for (int sl = (int)((int64_t)nL * t / nth); sl < s1; ++sl) {
         // the inputs of the landmarks kPf slots ahead (their edge runs sit at
@@ -1264,7 +1272,7 @@ int prepare(sqlm_ctx *c, int level) {
     });
   } else if (contig) {  // edge order (streaming reads): edge e of landmark l goes to its slot's base + (e - first edge)
     par([&](int t) {
-      bool bad = false;
+      uint8_t bad = 0;
       for (int64_t e = c->n_obs * t / nth; e < c->n_obs * (t + 1) / nth; ++e) {
         if (c->obs_level[e] != level) continue;
         const int l = c->obs_pt[e], sl = pt_slot[l];
@@ -1291,7 +1299,7 @@ int prepare(sqlm_ctx *c, int level) {
     });
     par([&](int t) {
       std::vector<int> &fill = base[t];
-      bool bad = false;
+      uint8_t bad = 0;
       for (int64_t e = ebeg(t); e < ebeg(t + 1); ++e) {
         if (c->obs_level[e] != level) continue;
         const int sl = pt_slot[c->obs_pt[e]];
@@ -1302,7 +1310,9 @@ int prepare(sqlm_ctx *c, int level) {
   }
   phase("  scatter");
   // inputs that are not all float32 values: the double arrays, from the same slot order
-  const bool obs_f32 = std::find(inexact.begin(), inexact.end(), 1) == inexact.end();
+  uint8_t obs_flg = 0;
+  for (uint8_t f : inexact) obs_flg |= f;
+  const bool obs_f32 = (obs_flg & 1) == 0, any_robust = (obs_flg & 2) != 0;
   if (!obs_f32) {
     int e = 0;
     if ((e = pinned(c, P_OBSUV, 2 * nE, obs_uv)) || (e = pinned(c, P_OBSINFO, nE, obs_info)) ||
@@ -1696,6 +1706,10 @@ int prepare(sqlm_ctx *c, int level) {
     const bool no_spec = getenv("SQLM_NO_SPEC") && atoi(getenv("SQLM_NO_SPEC")) != 0;
     c->no_pose_fuse = getenv("SQLM_NO_POSE_FUSE") != nullptr;
     c->spec = c->use_tiles && d.obs_P == nullptr && !no_spec;
+    c->trial_stores = getenv("SQLM_TRIAL_STORES") && atoi(getenv("SQLM_TRIAL_STORES")) != 0;
+    d.trial_stores = c->trial_stores ? 1 : 0;
+    // no robust edge: the weights are sqrt(info) at every state, written once by k_linearize
+    d.s_const = !any_robust && !c->trial_stores ? 1 : 0;
     // the side stream's fork / join (two event records, two waits: ~20 us of
     // host API time per trial) pays only when the pass is long enough to hide
     // (profiles/r03/ab_lba_cam_inline.log)
@@ -1710,7 +1724,8 @@ int prepare(sqlm_ctx *c, int level) {
   if (c->spec) {
     AL(B_LMR_NX, 8 * (size_t)nL, d.lm_R_nx);
     AL(B_LMB_NX, 4 * (size_t)nL, d.lm_b_nx);
-    AL(B_OBSS_NX, (size_t)nE, d.obs_s_nx);
+    if (d.s_const) d.obs_s_nx = d.obs_s;
+    else AL(B_OBSS_NX, (size_t)nE, d.obs_s_nx);
     AL(B_HPP_NX, 36 * (size_t)nP, d.Hpp_nx);
     AL(B_BP_NX, 8 * (size_t)nP, d.bp_nx);
   } else {
@@ -1833,8 +1848,7 @@ int prepare(sqlm_ctx *c, int level) {
 #undef AL
   SQLM_HIP_OK(hipMemsetAsync(d.partials, 0, sizeof(double) * kMaxPartials, c->stream));
   SQLM_HIP_OK(hipMemsetAsync(d.maxdiag, 0, sizeof(unsigned long long), c->stream));
-  SQLM_HIP_OK(hipMemsetAsync(d.obs_err, 0, sizeof(double) * 2 * std::max<int64_t>(nE, 1), c->stream));
-  if (d.obs_err3) SQLM_HIP_OK(hipMemsetAsync(d.obs_err3, 0, sizeof(double) * std::max<int64_t>(nE, 1), c->stream));
+  c->err_state = -1;  // no error evaluated yet (fetch_errors then delivers zeros)
   launch_pose_prep(d, 0, c->stream);
   phase("upload");
   if (ptime) {  // how long the queued copies and setup kernels still run after the host is done
@@ -1849,7 +1863,10 @@ int prepare(sqlm_ctx *c, int level) {
 // every active edge) into the caller-order host arrays: ~90 MB on config 4,
 // fetched only when a caller needs an edge chi2 (LBA outlier tags,
 // sqlm_get_edge_chi2) or before the next prepare() replaces them on the
-// device -- a GBA call that never asks does not pay for the copy.
+// device -- a GBA call that never asks does not pay for the copy. They are
+// evaluated only now, by k_edge_errors at the state the last linearization or
+// trial evaluated (err_state; that state is still on the device): the LM loop
+// stores no per-edge error.
 void ensure_host_errors(sqlm_ctx *c) {
   if (!c->err_zero) return;
   c->err_zero = false;
@@ -1873,6 +1890,12 @@ int fetch_errors(sqlm_ctx *c) {
   stage(P_RERR, 2 * (size_t)d.nE, err, 0);
   stage(P_RERR3, d.obs_err3 ? (size_t)d.nE : 0, err3, 1);
   stage(P_RLERR, (size_t)d.nLid, lerr, 2);
+  if (c->err_state < 0) {  // nothing evaluated since prepare(): zeros
+    if (d.nE) SQLM_HIP_OK(hipMemsetAsync(d.obs_err, 0, sizeof(double) * 2 * (size_t)d.nE, c->stream));
+    if (d.nE && d.obs_err3) SQLM_HIP_OK(hipMemsetAsync(d.obs_err3, 0, sizeof(double) * (size_t)d.nE, c->stream));
+  } else if (!c->trial_stores) {  // the errors of the last evaluated state, computed now
+    launch_edge_errors(d, c->err_state, c->stream);
+  }
   if (err3.size())
     SQLM_HIP_OK(hipMemcpyAsync(err3.data(), d.obs_err3, err3.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   if (d.nE) SQLM_HIP_OK(hipMemcpyAsync(err.data(), d.obs_err, err.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -1946,6 +1969,7 @@ int linearize(sqlm_ctx *c) {
     return SQLM_OK;
   }
   c->lin_timers = 2;  // + the camera pass on the side stream
+  c->err_state = 0;
   // the camera pass (H_pp, b_p, LiDAR) reads only the state, like the landmark
   // QR: fork it onto the side stream and join before anything consumes H_pp
   SQLM_HIP_OK(hipEventRecord(c->ev_fork, c->stream));
@@ -2151,6 +2175,7 @@ int trial_launch(sqlm_ctx *c, double lambda, bool &cam_after) {
   // 686 -> 647 it/s, the CR solve after them 0.54 -> 0.61 ms; profiles/r03/ab_upd_streams.log)
   // every bucket in one launch (the fused first bucket of a small problem
   // keeps its own launch: the fused form of the merged kernel measured slower)
+  c->err_state = 1;  // (also when the solve failed: the update then evaluates the state with dx = 0)
   if (!fuse && c->upd.nb > 0) {
     launch_landmark_update_all(d, c->upd, lambda, c->stream, c->spec);
   } else {
@@ -2190,6 +2215,7 @@ void swap_state(sqlm_ctx *c) {
   std::swap(d.pose_qt[0], d.pose_qt[1]);
   std::swap(d.pose_rt[0], d.pose_rt[1]);
   std::swap(d.X[0], d.X[1]);
+  if (c->err_state >= 0) c->err_state ^= 1;
   c->lin_valid = c->spec;
   if (c->spec) {  // the speculative linearization at the accepted state becomes current
     std::swap(d.lm_R, d.lm_R_nx);

@@ -146,13 +146,22 @@ struct DevProblem {
   int obs_f32 = 0;
   float *obs_q = nullptr;                   // [nE][4] (obs_f32)
   float *cam_q = nullptr;                   // [cam_obs][4] camera order (obs_f32)
+  // s_const: no active edge has a robust kernel, so the weight is sqrt(info)
+  // at every state: k_linearize writes it once, the speculative pass does not
+  // store it and obs_s_nx is obs_s itself (no second array)
   double *obs_s = nullptr;                  // [nE] sqrt(rho' info) at the linearization point
+  int s_const = 0;
   double *obs_P = nullptr;                  // [18][nE] H_lp blocks, SoA: row-kernel fallback only (else null)
-  double *obs_err = nullptr;                // [nE][2] last computed error (g2o _error)
+  // The LM loop does not store the errors: nothing on the device reads them.
+  // k_edge_errors fills obs_err / obs_err3 from the last evaluated state when
+  // the host asks (fetch_errors). trial_stores (SQLM_TRIAL_STORES=1): every
+  // linearization and trial stores them, and its weights, as before (A/B, tests)
+  double *obs_err = nullptr;                // [nE][2] error at the last evaluated state (g2o _error), on demand
+  int trial_stores = 0;
   // stereo edges (EdgeStereoSE3ProjectXYZ): has_stereo selects the ST kernels
   int has_stereo = 0;
   double *obs_ur = nullptr;                 // [nE] right-image u, < 0 = mono edge
-  double *obs_err3 = nullptr;               // [nE] third error component (0 for mono)
+  double *obs_err3 = nullptr;               // [nE] third error component (0 for mono), with obs_err
   double *pose_bf = nullptr;                // [n_pose] bf
   double *cam_ur = nullptr;                 // [cam_obs] obs_ur in camera order
   // cameras
@@ -320,6 +329,8 @@ struct Bucket {
 // kernel launchers (sqlm_kernels.hip). All asynchronous on `st`.
 void launch_pose_prep(const DevProblem &d, int buf, hipStream_t st);
 void launch_linearize(const DevProblem &d, const Bucket &b, int part_off, hipStream_t st);
+// every edge's error at state buffer buf (0 current / 1 trial) into obs_err / obs_err3
+void launch_edge_errors(const DevProblem &d, int buf, hipStream_t st);
 void launch_camera_pass(const DevProblem &d, hipStream_t st, bool spec = false);
 void launch_pose_maxdiag(const DevProblem &d, hipStream_t st);
 void launch_pose_diag(const DevProblem &d, hipStream_t st);

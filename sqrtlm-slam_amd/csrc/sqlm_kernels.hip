@@ -311,10 +311,14 @@ void launch_pose_prep(const DevProblem &d, int buf, hipStream_t st) {
 }
 
 // One edge of the landmark linearization at the state (prt_all, X): residual
-// and robust weight (to obs_err / s_out), the weighted Jacobian rows folded into
-// the landmark's R by Givens rotations, b_l, the Hessian diagonal g, chi2.
+// and robust weight, the weighted Jacobian rows folded into the landmark's R by
+// Givens rotations, b_l, the Hessian diagonal g, chi2.
 // k_linearize and the speculative pass of k_landmark_update call it in the same
 // order, so both produce the same bits.
+// The weight goes to s_out unless that is null (the speculative pass of a
+// problem without robust edges: the weight is sqrt(info) at every state). The
+// error is stored only under d.trial_stores: no kernel reads it, k_edge_errors
+// recomputes it when the host asks.
 template <bool ST>
 __device__ __forceinline__ void lin_edge(const DevProblem &d, const ObsIn &o, int e, const double *prt_all, double X0,
                                          double X1, double X2, double *s_out, bool want_P, double R[6], double &b0,
@@ -326,9 +330,11 @@ __device__ __forceinline__ void lin_edge(const DevProblem &d, const ObsIn &o, in
   const bool st = ST && o.ur >= 0.0;
   if (st) stereo_error(prt, X0, X1, X2, o.u, o.v, o.ur, bf, o.info, o.delta, m);
   else mono_error(prt, X0, X1, X2, o.u, o.v, o.info, o.delta, m);
-  store2(d.obs_err + 2 * e, m.e0, m.e1);
-  if (ST) d.obs_err3[e] = st ? m.e2 : 0.0;
-  s_out[e] = m.s;
+  if (d.trial_stores) {
+    store2(d.obs_err + 2 * e, m.e0, m.e1);
+    if (ST) d.obs_err3[e] = st ? m.e2 : 0.0;
+  }
+  if (s_out) s_out[e] = m.s;
   chi += m.chi_rob;
   double jl[6], jp[12], jl3[3] = {0, 0, 0}, jp3[6] = {0, 0, 0, 0, 0, 0};
   mono_jac(prt, m, jl, jp);
@@ -491,6 +497,37 @@ void launch_linearize(const DevProblem &d, const Bucket &b, int part_off, hipStr
 #undef SQLM_CASE
     default: break;
   }
+}
+
+// ---------------------------------------------------------------- edge errors
+
+// computeActiveErrors' _error of every edge at state buffer buf, one thread per
+// observation, into obs_err / obs_err3 in slot order. The LM loop keeps no
+// per-edge error; the host launches this before it copies them (fetch_errors).
+// The observation is read as the loop's kernels read it (load_obs) and goes
+// through the same mono_error / stereo_error with the stored landmark and pose
+// rows of that state, so the values are the ones the loop computed.
+template <bool ST>
+__global__ __launch_bounds__(256) void k_edge_errors(DevProblem d, int buf) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= d.nE) return;
+  const int e = (int)t;
+  const ObsIn o = load_obs<ST, false>(d, e, true);
+  const double *X = d.X[buf] + 4 * (int64_t)d.obs_lm[e];
+  const double *prt = d.pose_rt[buf] + 16 * o.cam;
+  const bool st = ST && o.ur >= 0.0;
+  MonoEval m;
+  if (st) stereo_error(prt, X[0], X[1], X[2], o.u, o.v, o.ur, d.pose_bf[o.cam], o.info, o.delta, m);
+  else mono_error(prt, X[0], X[1], X[2], o.u, o.v, o.info, o.delta, m);
+  store2(d.obs_err + 2 * t, m.e0, m.e1);
+  if (ST) d.obs_err3[e] = st ? m.e2 : 0.0;
+}
+
+void launch_edge_errors(const DevProblem &d, int buf, hipStream_t st) {
+  if (d.nE <= 0) return;
+  const dim3 grid((unsigned)((d.nE + 255) / 256));
+  if (d.has_stereo) hipLaunchKernelGGL(k_edge_errors<true>, grid, dim3(256), 0, st, d, buf);
+  else hipLaunchKernelGGL(k_edge_errors<false>, grid, dim3(256), 0, st, d, buf);
 }
 
 // ---------------------------------------------------------------- camera pass
@@ -2208,13 +2245,14 @@ __device__ __forceinline__ void landmark_update_body(const DevProblem &d, int sl
         sc_acc += dl0 * (lambda * dl0 + bl[0]) + dl1 * (lambda * dl1 + bl[1]) + dl2 * (lambda * dl2 + bl[2]);
       }
       if (SPEC) {  // the next linearization at the trial state (used if the trial is accepted)
+        double *s_nx = d.s_const ? nullptr : d.obs_s_nx;  // constant weights are not written again
 #pragma unroll
         for (int i = 0; i < kObsPreload; ++i) {
           const int e = beg + lane + i * W;
-          if (e < end) lin_edge<ST>(d, o[i], e, P1, X0, X1, X2, d.obs_s_nx, false, R, b0, b1, b2, g0, g1, g2, chi);
+          if (e < end) lin_edge<ST>(d, o[i], e, P1, X0, X1, X2, s_nx, false, R, b0, b1, b2, g0, g1, g2, chi);
         }
         stream2([&](const ObsIn &oi, int e) {
-          lin_edge<ST>(d, oi, e, P1, X0, X1, X2, d.obs_s_nx, false, R, b0, b1, b2, g0, g1, g2, chi);
+          lin_edge<ST>(d, oi, e, P1, X0, X1, X2, s_nx, false, R, b0, b1, b2, g0, g1, g2, chi);
         });
       } else {
         auto trial_err = [&](const ObsIn &o, int e) {
@@ -2222,8 +2260,10 @@ __device__ __forceinline__ void landmark_update_body(const DevProblem &d, int sl
           const double *prt = P1 + 16 * o.cam;
           if (ST && o.ur >= 0.0) stereo_error(prt, X0, X1, X2, o.u, o.v, o.ur, d.pose_bf[o.cam], o.info, o.delta, m);
           else mono_error(prt, X0, X1, X2, o.u, o.v, o.info, o.delta, m);
-          store2(d.obs_err + 2 * e, m.e0, m.e1);
-          if (ST) d.obs_err3[e] = o.ur >= 0.0 ? m.e2 : 0.0;
+          if (d.trial_stores) {
+            store2(d.obs_err + 2 * e, m.e0, m.e1);
+            if (ST) d.obs_err3[e] = o.ur >= 0.0 ? m.e2 : 0.0;
+          }
           chi += m.chi_rob;
         };
 #pragma unroll
