@@ -1,5 +1,5 @@
-// sqlm_internal.h — shared between the host LM driver (sqlm_api.cpp) and the
-// HIP kernels (sqlm_kernels.hip). Not part of the public ABI.
+// sqlm_internal.h — shared between the host side (setup sqlm_prepare.cpp / sqlm_plan.cpp,
+// LM driver sqlm_lm.cpp, ABI sqlm_api.cpp) and the HIP kernels (sqlm_kernels.hip). Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

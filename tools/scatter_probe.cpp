@@ -1,5 +1,5 @@
 // scatter_probe — host-side timing of the setup's observation scatter
-// (sqlm_api.cpp prepare(): edges -> landmark slot order) on synthetic data of
+// (sqlm_plan.cpp plan_scatter(): edges -> landmark slot order) on synthetic data of
 // config-4 shape: 5M edges in landmark runs of 2..18, 500k landmarks whose
 // slots are a shuffled order (the span sort). Variants: edge order (writes
 // scattered), slot order (reads scattered) with software prefetch 0 / 8 / 16
