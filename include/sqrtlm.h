@@ -388,8 +388,14 @@ int sqlm_get_exec_info(sqlm_ctx *ctx, int out[8]);
  * complement's right-hand side, and dx [6 n_free] = the camera step the trial
  * applied as T <- exp(dx) T (zero if the solve met a non-positive pivot), both
  * in free-camera (hessianIndex) order, tangent order [omega; upsilon].
- * Synchronises the context stream. SQLM_ERR_STATE without a prepared problem,
- * before any trial has run, or on a sharded context. */
+ * Synchronises the context stream. SQLM_ERR_STATE without a prepared problem
+ * or before any trial has run.
+ * On a sharded context (every rank indexes the same free cameras): rank 0, and
+ * the one-rank self-loop, return the system it solved -- g summed over the
+ * ranks -- and its solution; a rank >= 1 returns in dx the step rank 0
+ * broadcast (the same bits) and in g its own share of the right-hand side as
+ * it was sent to rank 0, meaningful only inside that rank's row range (the
+ * free cameras its own edges touch; zero elsewhere). */
 int sqlm_get_last_step(sqlm_ctx *ctx, double *g, double *dx);
 
 /* Converter::toSE3Quat / toCvMat(SE3Quat) (src/utils/Converter.cc:55-79,98-109):

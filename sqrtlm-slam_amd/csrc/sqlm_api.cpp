@@ -642,13 +642,19 @@ int sqlm_get_exec_info(sqlm_ctx *c, int out[8]) {
 
 int sqlm_get_last_step(sqlm_ctx *c, double *g, double *dx) {
   if (!c || !g || !dx) return SQLM_ERR_INVALID_ARG;
-  if (!c->has_problem || !c->prepared || !c->step_valid || c->comm.enabled()) return SQLM_ERR_STATE;
+  if (!c->has_problem || !c->prepared || !c->step_valid) return SQLM_ERR_STATE;
   const size_t n = 6 * (size_t)c->d.nP;
   if (n == 0) return SQLM_OK;
   if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
   // g: rcs_put_g / k_rcs; dx: the dense solve's copy, or on a CR layout the
   // pose update's copy of the CR / border solution. Nothing after the trial
   // (speculative camera pass, finish) writes either.
+  // Sharded: rank 0's g is k_gather_add's sum over the ranks (the last writer
+  // of d.g; the solves only read it), a rank >= 1's g its own share as it was
+  // sent (rows outside the rank's range keep what rcs_put_g / k_rcs put there).
+  // dx is the solves' copy on rank 0 (the CR solve gathers into d.dx there:
+  // the pose update does not read the CR solution on a sharded run) and the
+  // broadcast's elsewhere; the flag rides in slot 6 nP, past what is copied.
   SQLM_HIP_OK(hipMemcpyAsync(g, c->d.g, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   SQLM_HIP_OK(hipMemcpyAsync(dx, c->d.dx, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   SQLM_HIP_OK(hipStreamSynchronize(c->stream));

@@ -120,7 +120,11 @@ class Context:
     def last_step(self):
         """(g, dx) of the most recent LM trial (sqlm_get_last_step): the reduced
         camera system's right-hand side and the camera step, each (n_free, 6) in
-        free-camera order, g2o's sign convention (H dx = b, b = -J^T W r)."""
+        free-camera order, g2o's sign convention (H dx = b, b = -J^T W r).
+        On a sharded context rank 0 (and the self-loop) returns the system it
+        solved, g summed over the ranks; a rank >= 1 returns the broadcast dx
+        and, in g, its own share as it was sent: zero outside the free cameras
+        its own edges touch, not the full right-hand side inside them."""
         n = self.rcs_layout()["n_free"]
         g, dx = np.zeros((n, 6)), np.zeros((n, 6))
         check(lib().sqlm_get_last_step(self._h, ptr(g), ptr(dx)), "sqlm_get_last_step")

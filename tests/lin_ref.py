@@ -299,7 +299,9 @@ def _solve_refined(S, g):
     return x, steps
 
 
-def first_trial(prob, lam, dtype=LD, level=0) -> Trial:
+def first_trial(prob, lam, dtype=LD, level=0, solve=True) -> Trial:
+    """solve=False stops after the blocks H_pp, b_p, H_ll, b_l (S, g, dx, dl are
+    None): all lambda_init needs, and lam = 0 may leave an H_ll singular."""
     T = dtype
     ed = edges(prob, T, level=level)
     lid = lidar_edges(prob, T, level=level) if prob.n_lid else None
@@ -341,6 +343,8 @@ def first_trial(prob, lam, dtype=LD, level=0) -> Trial:
         bp = bp - _segsum(Ji * lid.e[:, None], lh_, nP)
         chi2_0 = chi2_0 + lid.chi2.sum()
     Hpp[:, range(6), range(6)] += lam
+    if not solve:
+        return Trial(free, lms, Hpp, bp, Hll, bl, None, None, None, None, chi2_0, 0)
 
     # H_pl blocks, one per (landmark, free camera): repeated observations add up
     key = lh[fe] * nP + ph
@@ -385,6 +389,29 @@ def first_trial(prob, lam, dtype=LD, level=0) -> Trial:
     return Trial(free, lms, Hpp, bp, Hll, bl, S, g, dx, dl, chi2_0, steps)
 
 
+# ------------------------------------------------------------------ lambda_0
+
+def max_diagonal(prob, dtype=LD, level=0):
+    """(largest |diagonal entry| of J^T W J over all free vertices, "pose" or
+    "point", the pose / point id it sits on): the blocks of an undamped
+    first_trial (lam = 0)."""
+    tr = first_trial(prob, 0, dtype, level, solve=False)
+    dp = np.abs(tr.Hpp[:, range(6), range(6)]).max(axis=1) if tr.free.size else np.zeros(0, dtype)
+    dl = np.abs(tr.Hll[:, range(3), range(3)]).max(axis=1) if tr.lms.size else np.zeros(0, dtype)
+    ip = int(np.argmax(dp)) if dp.size else -1
+    il = int(np.argmax(dl)) if dl.size else -1
+    if il < 0 or (ip >= 0 and dp[ip] >= dl[il]):
+        return dp[ip], "pose", int(tr.free[ip])
+    return dl[il], "point", int(tr.lms[il])
+
+
+def lambda_init(prob, dtype=LD, level=0):
+    """OptimizationAlgorithmLevenberg::computeLambdaInit (levenberg.cpp:166-180,
+    oracle/g2o_ref.c max_diagonal): 1e-5 x the largest diagonal entry of
+    J^T W J over all free vertices, poses and landmarks alike, in `dtype`."""
+    return dtype(1e-5) * max_diagonal(prob, dtype, level)[0]
+
+
 # ------------------------------------------------------------------ rounding spread
 
 def _rel(a, b):
@@ -409,6 +436,17 @@ def spreads(prob, lam, ref: Trial | None = None, level=0):
     Trial, float64 Trial)."""
     ref = first_trial(prob, lam, LD, level) if ref is None else ref
     f64 = first_trial(prob, lam, np.float64, level)
+    out = dict(g=_rel(f64.g, ref.g), dx=_rel(f64.dx, ref.dx), dl=_rel(f64.dl, ref.dl),
+               chi2_0=_rel(f64.chi2_0, ref.chi2_0))
+    return out, ref, f64
+
+
+def spreads_lambda_init(prob, level=0):
+    """spreads() of the trial at lambda_0 = lambda_init: the float64 side
+    evaluates its own lambda_0 in float64, so the spread holds that rounding
+    too. Returns (dict, longdouble Trial, float64 Trial)."""
+    ref = first_trial(prob, lambda_init(prob, LD, level), LD, level)
+    f64 = first_trial(prob, lambda_init(prob, np.float64, level), np.float64, level)
     out = dict(g=_rel(f64.g, ref.g), dx=_rel(f64.dx, ref.dx), dl=_rel(f64.dl, ref.dl),
                chi2_0=_rel(f64.chi2_0, ref.chi2_0))
     return out, ref, f64

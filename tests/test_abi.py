@@ -57,6 +57,9 @@ def test_null_and_invalid_arguments():
     assert L.sqlm_optimize(None, 0, 1, C.c_double(0), None, None, None) == -1
     buf = (C.c_double * 6)()
     assert L.sqlm_get_last_step(None, buf, buf) == -1
+    hdr = open(os.path.join(ROOT, "include", "sqrtlm.h")).read()
+    doc = hdr[:hdr.index("int sqlm_get_last_step")].rsplit("*/", 2)[-2]   # its comment: sharded contexts answer
+    assert "SQLM_ERR_STATE without a prepared problem" in doc and "On a sharded context" in doc
     assert L.sqlm_get_lidar_error(None, buf) == -1
     assert L.sqlm_eg_get_last_step(None, buf, buf) == -1
     out = (C.c_int * 8)()

@@ -130,11 +130,13 @@ def _maxrel(a, b):
     return float(np.abs(a - b).max() / np.abs(b).max())
 
 
-def ratios(oracle, name, run):
-    """GPU error / reference spread per quantity (and both, for the table)."""
+def ratios(oracle, name, run, reference=None):
+    """GPU error / reference spread per quantity (and both, for the table).
+    reference: (spreads, longdouble trial, float64 trial) in place of the
+    case's own (the same problem at another lambda)."""
     prob = _problem(name)
     level = _level(name)
-    sp, ref, f64 = _reference(name)
+    sp, ref, f64 = reference or _reference(name)
     out = {}
 
     def put(key, err, spread):

@@ -251,3 +251,77 @@ def test_no_lidar_is_unchanged():
         assert np.array_equal(getattr(a, k), getattr(b, k)), k
     assert a.chi2_0 == b.chi2_0
     assert lin_ref.chi2(prob, dtype=np.float64) == lin_ref.chi2(off, dtype=np.float64)
+
+
+# ------------------------------------------------------------------ sharded first trial (CPU side)
+
+import sharded_first_trial_cases as shc  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(shc.LAMBDA0))
+def test_lambda_init_matches_oracle(oracle, name):
+    """lin_ref.lambda_init against the oracle's computeLambdaInit: the oracle's
+    first trial at user_lambda = 0 (its own lambda_0) and at user_lambda =
+    float(lambda_init(longdouble)) give the same chi2 within 100 x max(spread,
+    4 eps), the spread being that of the trial chi2 between the reference's
+    float64 and longdouble evaluations, each with its own lambda_0. The oracle
+    accepts that trial, and the largest diagonal entry sits on a pose that at
+    least two ranks see at worlds 2 and 3 under the run's owner map."""
+    prob = shc.problem(name)
+    lam_hi, lam_lo = lin_ref.lambda_init(prob, LD), lin_ref.lambda_init(prob, np.float64)
+    assert lam_hi.dtype == LD and float(abs(LD(lam_lo) - lam_hi) / lam_hi) <= 16 * EPS
+    st = {}
+    for key, lam in (("own", 0.0), ("ref", float(lam_hi))):
+        og = oracle.OracleGraph(prob)
+        n, st[key] = og.optimize(0, 1, user_lambda=lam)
+        assert n == 1 and st[key]["trace_trials"] == [1], st[key]
+    sp, ref, f64 = lin_ref.spreads_lambda_init(prob)
+    chi = {}
+    for key, tr in (("hi", ref), ("lo", f64)):
+        q, t = lin_ref.oplus_poses(oracle, prob, tr.free, tr.dx.astype(np.float64))
+        chi[key] = lin_ref.chi2(prob, q, t, prob.pt + tr.dl.astype(np.float64), LD if key == "hi" else np.float64)
+    spread = float(abs(LD(chi["lo"]) - chi["hi"]) / chi["hi"])
+    a, b = LD(st["own"]["trace_chi2"][0]), LD(st["ref"]["trace_chi2"][0])
+    print(f"{name}: lambda_0 {float(lam_hi):.17g} chi2 own {float(a):.17g} ref {float(b):.17g} spread {spread:.2e}")
+    assert float(abs(a - b) / b) <= 100 * max(spread, 4 * EPS)
+    assert float(abs(b - chi["hi"]) / chi["hi"]) <= 100 * max(spread, 4 * EPS)
+    # the oracle's lambda after the trial is lambda_0 times a factor in [1/3, 2/3]
+    assert 1 / 3 - 1e-12 <= st["own"]["trace_lambda"][0] / float(lam_hi) <= 2 / 3 + 1e-12
+    val, kind, pose = lin_ref.max_diagonal(prob)
+    assert kind == "pose" and lin_ref.max_diagonal(prob, np.float64)[1:] == (kind, pose)
+    for world in shc.WORLDS:
+        own = shc.owner_map(name, world)
+        assert np.unique(own[prob.obs_pt[prob.obs_pose == pose]]).size >= 2, (name, world, pose)
+
+
+@pytest.mark.parametrize("name,world", shc.pairs())
+def test_shard_geometry(name, world):
+    """Every (case, world) of tests/test_gpu_first_trial_sharded.py: at least
+    two ranks' row ranges overlap, so k_gather_add sums; the degenerate cases
+    have the property they are named for."""
+    prob = shc.problem(name)
+    rng = [shc.row_range(name, world, r) for r in range(world)]
+    locs = [shc.local_problem(name, world, r) for r in range(world)]
+    assert sum(loc.n_obs for loc in locs) == prob.n_obs and sum(loc.n_pt for loc in locs) == prob.n_pt
+    nP = shc.free_cameras(name).size
+    assert nP == lin_ref.first_trial(prob, 1.0, np.float64, shc.level(name), solve=False).free.size
+    if name in shc.LIDAR_ONLY:
+        # rank 0 alone holds active edges (LiDAR); the others send nothing
+        assert rng[0] == (0, nP) and all(r == (0, 0) for r in rng[1:])
+        assert all(loc.n_obs > 0 and not np.any(loc.obs_level == shc.level(name)) for loc in locs)
+        return
+    assert shc.overlapping_ranks(name, world), rng
+    if name == "long_red":       # every rank touches every free camera
+        assert all(r == (0, nP) for r in rng)
+    if name == "fixed_only_rank":
+        fo = shc.fixed_only_landmarks(prob)
+        own = shc.owner_map(name, world)
+        assert fo.any() and np.array_equal(own == 1, fo)
+        assert locs[1].n_obs > 0 and np.all(prob.pose_fixed[locs[1].obs_pose] != 0) and rng[1] == (0, 0)
+        assert rng[0][1] > rng[0][0] and rng[2][1] > rng[2][0]
+    if name == "interleaved":
+        assert np.array_equal(shc.owner_map(name, world), np.arange(prob.n_pt) % 3)
+        assert all(r == (0, nP) for r in rng)           # every rank spans the whole band
+    if name == "empty_rank":
+        assert locs[1].n_pt == 0 and locs[1].n_obs == 0 and rng[1] == (0, 0)
+        assert locs[0].n_pt > 0 and locs[2].n_pt > 0

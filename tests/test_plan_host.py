@@ -33,3 +33,18 @@ def test_planner_against_naive_references():
     assert col("empty", "status") == "-7"  # SQLM_ERR_STATE: nothing to optimize
     assert col("dup", "dups") == "1" and col("non-f32", "f32") == "0"
     assert int(col("big", "nE")) >= 2 * 131072 and int(col("big", "threads").split("/")[0]) >= 1
+
+
+def test_planner_on_a_shard_without_landmarks():
+    """`plan_check shard`: one rank of a sharded run that owns no landmark
+    (n_pt = n_obs = 0). Its free cameras come from the other ranks (prepare()
+    ORs the ranks' active poses between the planner's first two stages); every
+    edge list, bucket and tile list is empty and S is its diagonal."""
+    tools = os.path.join(ROOT, "tools")
+    subprocess.run(["make", "-s", "-C", tools, "plan_check"], check=True)
+    r = subprocess.run([os.path.join(tools, "plan_check"), "shard"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln.split() for ln in r.stdout.splitlines() if ln.strip()]
+    assert [ln[:2] for ln in lines] == [["ok", "empty-shard"]], r.stdout
+    col = lambda key: lines[0][lines[0].index(key) + 1]
+    assert col("status") == "0" and col("nP") == "9" and col("nL") == "0" and col("nE") == "0" and col("tiles") == "0"

@@ -126,3 +126,65 @@ def test_balance_at_eight_ranks_full_size():
         assert cams[-1] - cams[0] + 1 == cams.size  # contiguous window
         assert cams.size <= prob.n_pose / 8 + 2 * 18
     assert max(obs) - min(obs) <= 2 * 18 + 1
+
+
+def _owner_cases():
+    """(problem, owner map, world): contiguous ranges, an interleaved map, a
+    map with an empty middle rank; the problem has stereo edges, LiDAR edges
+    with levels and fixed cameras."""
+    from sqrtlm.shard import range_owner
+    prob = synth.add_stereo(synth.make_problem(20, 300, k_min=2, k_max=8, seed=5, n_fixed=2), 0.5, seed=5)
+    prob = synth.add_lidar_flat(prob, pose=7, n=12, seed=2)
+    prob.meta["lid_level"] = (np.arange(prob.n_lid) % 2).astype(np.uint8)
+    inter = np.arange(prob.n_pt) % 3
+    hole = np.where(np.arange(prob.n_pt) < prob.n_pt // 2, 0, 2)
+    return [(prob, range_owner(prob, 3), 3), (prob, inter, 3), (prob, hole, 3)]
+
+
+OBS_FIELDS = ("obs_pose", "obs_uv", "obs_info", "obs_delta", "obs_level", "obs_ur")
+
+
+@pytest.mark.parametrize("case", range(3))
+def test_shard_by_owner_partitions_and_restores(case):
+    from sqrtlm.shard import shard_by_owner
+    prob, owner, world = _owner_cases()[case]
+    locs = [shard_by_owner(prob, owner, r) for r in range(world)]
+    # the shards partition the observations, each in its original relative order
+    edge_of = [np.nonzero(owner[prob.obs_pt] == r)[0] for r in range(world)]
+    assert sum(loc.n_obs for loc in locs) == prob.n_obs
+    assert np.array_equal(np.sort(np.concatenate(edge_of)), np.arange(prob.n_obs))
+    pt_of = [np.nonzero(owner == r)[0] for r in range(world)]
+    for r, loc in enumerate(locs):
+        for k in OBS_FIELDS:
+            np.testing.assert_array_equal(getattr(loc, k), getattr(prob, k)[edge_of[r]], err_msg=k)
+        np.testing.assert_array_equal(pt_of[r][loc.obs_pt], prob.obs_pt[edge_of[r]])   # the same landmark
+        for k in ("pose_q", "pose_t", "pose_fixed", "intr", "pose_bf"):
+            np.testing.assert_array_equal(getattr(loc, k), getattr(prob, k), err_msg=k)
+        assert loc.n_lid == (prob.n_lid if r == 0 else 0)
+        assert ("lid_level" in loc.meta) == (r == 0)
+    np.testing.assert_array_equal(locs[0].meta["lid_level"], prob.meta["lid_level"])
+    # re-assembling the points by owner restores the order
+    X = np.zeros_like(prob.pt)
+    for r, loc in enumerate(locs):
+        X[owner == r] = loc.pt
+    np.testing.assert_array_equal(X, prob.pt)
+    # the union of the shards' free cameras is the problem's
+    free = lambda p: set(np.unique(p.obs_pose[p.pose_fixed[p.obs_pose] == 0]).tolist())
+    assert set().union(*(free(loc) for loc in locs)) == free(prob)
+    if case == 2:
+        assert locs[1].n_pt == 0 and locs[1].n_obs == 0
+
+
+def test_shard_is_the_contiguous_owner_map():
+    """shard() against the slices it stands for, field by field."""
+    prob = _owner_cases()[0][0]
+    for world in (2, 3):
+        for r, (lo, hi) in enumerate(landmark_ranges(prob, world)):
+            loc = shard(prob, r, world)
+            sel = (prob.obs_pt >= lo) & (prob.obs_pt < hi)
+            np.testing.assert_array_equal(loc.pt, prob.pt[lo:hi])
+            np.testing.assert_array_equal(loc.obs_pt, prob.obs_pt[sel] - lo)
+            assert loc.obs_pt.dtype == np.int32
+            for k in OBS_FIELDS:
+                np.testing.assert_array_equal(getattr(loc, k), getattr(prob, k)[sel], err_msg=k)
+    assert shard(prob, 0, 1) is prob

@@ -58,6 +58,7 @@ struct Graph {
   std::vector<int32_t> lid_pose;
   std::vector<double> lid_pc, lid_pw, lid_n, lid_info;
   std::vector<uint8_t> lid_level;
+  std::vector<uint8_t> ext_act;  // a shard of a sharded run: the poses the other ranks' edges make active
   int expect_status = SQLM_OK;
   int expect_solver = 0;  // 0 any, 1 band, 2 band + border, 3 dense
   int expect_f32 = -1, expect_robust = -1, expect_dups = -1, expect_tiles = -1;  // -1 any
@@ -143,6 +144,8 @@ void run_plan(const Graph &G, Out &r) {
   const GraphView g = G.view();
   SetupPlan &pl = r.pl;
   plan_active_set(g, true, r.ps, pl, phase);
+  // prepare() ORs the ranks' pose_act here (all-reduce max)
+  for (size_t p = 0; p < G.ext_act.size(); ++p) r.ps.pose_act[p] |= G.ext_act[p];
   if ((r.status = plan_slots(g, r.ps, pl, phase))) return;
   const size_t nE = (size_t)pl.nE;
   r.dev_edge.assign(nE, -1);
@@ -221,6 +224,7 @@ Naive naive_active(const Graph &G) {
       n.lid_act.push_back((int64_t)e);
       n.pose_act[G.lid_pose[e]] = 1;
     }
+  for (size_t p = 0; p < G.ext_act.size(); ++p) n.pose_act[p] |= G.ext_act[p];
   n.phidx.assign(G.n_pose, -1);
   for (int p = 0; p < G.n_pose; ++p)
     if (n.pose_act[p] && !G.pose_fixed[p]) { n.phidx[p] = (int)n.hidxp.size(); n.hidxp.push_back(p); }
@@ -675,9 +679,38 @@ Graph shuffled(const Graph &G, std::vector<int64_t> &relabel) {
   return S;
 }
 
+// A rank of a sharded run that owns no landmark (n_pt = n_obs = 0): the
+// other ranks' cameras are free here too, every list is empty, S is its diagonal
+void check_empty_shard() {
+  Graph es;
+  es.name = "empty-shard";
+  es.n_pose = 12;
+  es.pose_fixed.assign(12, 0);
+  es.pose_fixed[0] = es.pose_fixed[1] = 1;
+  es.ext_act.assign(12, 1);
+  es.ext_act[11] = 0;
+  es.expect_tiles = 1;
+  Out eo;
+  check_graph(es, &eo);
+  g_ctx = "empty-shard";
+  CHECK(eo.pl.nP == 9 && eo.pl.nL == 0 && eo.pl.nE == 0 && eo.pl.n_lm_parts == 0, "empty shard: sizes");
+  CHECK(eo.pl.buckets.empty() && eo.pl.upd.nb == 0 && eo.pl.upd_rng.empty(), "empty shard: no update launch");
+  CHECK(eo.ps.tp.lm_ptr.size() == 1 && eo.ps.tp.red_off.empty() && eo.ps.tp.gred_off.empty(), "empty shard: no tiles");
+  CHECK((int)eo.ps.tp.red_ptr.size() == eo.pl.s_row[eo.pl.nP] + 1 && (int)eo.ps.tp.gred_ptr.size() == eo.pl.nP + 1,
+        "empty shard: reduction list pointers cover the pattern");
+  CHECK(eo.sh_cam_ptr == std::vector<int>(10, 0) && eo.sh_cam_obs.empty(), "empty shard: camera CSR");
+  CHECK(eo.pl.lm_begin == std::vector<int>(1, 0) && eo.pl.slot_pt.empty(), "empty shard: lm_begin");
+}
+
 }  // namespace
 
-int main() {
+// No argument: the graphs of an unsharded setup. "shard": the graphs that stand
+// for one rank of a sharded run.
+int main(int argc, char **argv) {
+  if (argc > 1 && std::string(argv[1]) == "shard") {
+    check_empty_shard();
+    return 0;
+  }
   // 1. the smoke shape: band only
   Graph smoke = windowed("smoke", 12, 300, 3, 2, 1);
   smoke.expect_solver = 1; smoke.expect_f32 = 1; smoke.expect_robust = 0; smoke.expect_dups = 0; smoke.expect_tiles = 1;
