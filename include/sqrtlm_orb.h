@@ -9,7 +9,9 @@
  * (src/frontend/ORBmatcher.cc:573-718, :2096-2116). Frame::ExtractORB
  * (src/data_structure/Frame.cc) calls the extractor once per image; the
  * adapter replaces that call with sqlm_orb_extract and copies the arrays into
- * cv::KeyPoint / cv::Mat.
+ * cv::KeyPoint / cv::Mat. The last section is the DBoW2
+ * vocabulary: ORBVocabulary::transform (Frame / KeyFrame::ComputeBoW) and
+ * ORBVocabulary::score for a batch of keyframes.
  *
  * Contexts come from sqrtlm.h (sqlm_ctx_create); the calls run on the
  * context's HIP stream. Status codes as in sqrtlm.h.
@@ -213,6 +215,79 @@ int sqlm_orb_search_for_triangulation(sqlm_ctx *ctx, const sqlm_bow_frame *K1, c
                                       const float *C1, const float *T2w, const float *cam2,
                                       const float *scale_factors2, int n_levels2, const float *F12, int only_stereo,
                                       int check_ori, int32_t *m12, int *n_matches);
+
+/* ---- DBoW2 vocabulary: BoW transform and batched L1 score ----
+ *
+ * ORBVocabulary (TemplatedVocabulary<FORB::TDescriptor, FORB>) as
+ * loadFromTextFile builds it (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:
+ * 1374-1475): a node's id is its read order, node 0 is the root, a node's
+ * children are the nodes that name it as parent in ascending id, and word ids
+ * number the is_word nodes in ascending node id.
+ *
+ * sqlm_voc_create checks its arguments on the host before the device is
+ * touched. SQLM_ERR_INVALID_ARG: a NULL array, k outside 1..20, L outside
+ * 1..10 (the loader's limits), n_nodes < 2, parent[i] outside [0, i), more
+ * than k children, a word with children, a node without children that is not a
+ * word (the reference would descend into it and read word 0: an accident of
+ * the loader, not kept). SQLM_ERR_UNSUPPORTED: anything but scoring = 0
+ * (L1_NORM) and weighting = 0 (TF_IDF), ORBvoc's header values. A leaf may
+ * sit above or below depth L; the descent ends where the tree does.
+ *
+ * The object is immutable and belongs to a device, not to a context: the
+ * contexts of that device share one copy (48 bytes per node and 8 per word:
+ * about 60 MB for the 1,111,111 nodes of ORBvoc). A call whose context is on another
+ * device answers SQLM_ERR_INVALID_ARG. Destroy it after the last call that
+ * uses it has returned. */
+typedef struct sqlm_voc sqlm_voc;
+int sqlm_voc_create(int device, int k, int L, int scoring, int weighting, int32_t n_nodes,
+                    const int32_t *parent,  /* [n_nodes]; node 0 is the root, parent[i] < i for i > 0 */
+                    const uint8_t *is_word, /* [n_nodes] */
+                    const uint8_t *desc,    /* [n_nodes][32]; the root's is ignored */
+                    const double *weight,   /* [n_nodes]; read for words only */
+                    sqlm_voc **out);
+int sqlm_voc_destroy(sqlm_voc *voc);
+/* k, L, n_nodes, n_words, max children, max leaf depth, min leaf depth, device */
+int sqlm_voc_info(const sqlm_voc *voc, int32_t out[8]);
+
+/* TemplatedVocabulary::transform(features, v, fv, levelsup) (:1142-1212,
+ * :1246-1295) for n_img images at once; image j owns the features
+ * [feat_off[j], feat_off[j+1]) of desc (feat_off[0] = 0).
+ *
+ * Per feature: descend from the root, at each node to the child of smallest
+ * Hamming distance (the first such child in children order: the reference's
+ * strict <), until a node without children. word[i] = that leaf's word id;
+ * node[i] = the caller's id of the node chosen at depth L - levelsup, the
+ * FeatureVector entry in the form sqlm_bow_frame.node takes. L - levelsup <= 0
+ * gives node 0. A leaf reached above that depth gives the leaf's own node id:
+ * the reference leaves nid uninitialised there, so this value is this
+ * library's choice. A word of weight <= 0 is a stop word: word[i] = node[i] =
+ * -1 and the feature enters neither vector.
+ *
+ * Per image, the BowVector: entries [bow_off[j], bow_off[j+1]) of bow_word
+ * (ascending) and bow_value. A word seen n times has its weight added n times
+ * in feature order (BowVector::addWeight), then the vector is L1-normalised as
+ * BowVector::normalize does it: norm = the sequential sum of fabs in ascending
+ * word id, each value divided by it if norm > 0. At most n_feat entries in
+ * all. n_img = 0 is valid and does not touch the device. */
+int sqlm_bow_transform(sqlm_ctx *ctx, const sqlm_voc *voc, int n_img,
+                       const int64_t *feat_off,   /* [n_img+1] CSR over the features of each image */
+                       const uint8_t *desc,       /* [n_feat][32] */
+                       int levelsup,
+                       int32_t *word, int32_t *node,              /* [n_feat] */
+                       int64_t *bow_off, int32_t *bow_word, double *bow_value); /* [n_img+1], [<= n_feat] x2 */
+
+/* L1Scoring::score(query, db[j]) (ScoringObject.cpp:23-68) for n_db vectors:
+ * database vector j owns entries [db_off[j], db_off[j+1]) (db_off[0] = 0).
+ * score[j] = -sum / 2.0 with sum = the chain, in ascending word id, of
+ * fabs(vi - wi) - fabs(vi) - fabs(wi) over the common words (vi the query's
+ * value); no common word gives -0.0, as the reference does. n_common[j] (may
+ * be NULL) = the number of common words, the count KeyFrameDatabase::
+ * DetectLoopCandidates takes from its inverted file. Word arrays must be
+ * strictly ascending and >= 0 (checked on the host: SQLM_ERR_INVALID_ARG).
+ * n_db = 0 and nq = 0 are valid; nq = 0 scores -0.0 everywhere. */
+int sqlm_bow_score(sqlm_ctx *ctx, int64_t nq, const int32_t *q_word, const double *q_value,
+                   int n_db, const int64_t *db_off, const int32_t *db_word, const double *db_value,
+                   double *score, int32_t *n_common);  /* [n_db] each; n_common may be NULL */
 
 /* Bench helper: time `reps` extractions of one image (input uploaded once;
  * timed region = the whole device pipeline incl. the host quadtree step).

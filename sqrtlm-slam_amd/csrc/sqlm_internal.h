@@ -617,4 +617,28 @@ int orb_search_for_triangulation(OrbEngine *e, const struct sqlm_bow_frame *K1, 
                                  int n_levels2, const float *F12, int only_stereo, int check_ori, int32_t *m12,
                                  int *n_matches);
 
+// DBoW2 vocabulary (sqlm_bow.cpp, kernels sqlm_bow.hip). The tree on the
+// device is renumbered breadth first, children in ascending caller id, so the
+// children of a node are one contiguous run of 32-byte descriptors.
+constexpr int kBowGroup = 16;         // lanes that share one feature / one database vector
+constexpr int kBowScoreLds = 4096;    // query entries k_bow_score keeps in LDS (48 KiB); longer queries are read from memory
+struct BowNode {                      // one node in breadth-first numbering
+  int32_t child_begin, child_count;   // its children's run
+  int32_t orig;                       // the caller's node id
+  int32_t word;                       // childless nodes: the word id, -1 for a stop word (weight <= 0)
+};
+struct BowVocDev {
+  const uint4 *desc = nullptr;        // [n_nodes][2]
+  const BowNode *tab = nullptr;       // [n_nodes]
+  const double *weight = nullptr;     // [n_words]
+  int32_t root_count = 0, max_depth = 0;
+};
+void launch_bow_descend(const BowVocDev &v, const uint4 *feat, int n_feat, int nid_level, int32_t *word,
+                        int32_t *node, double *weight, hipStream_t st);
+void launch_bow_score(int nq, const int32_t *q_word, const double *q_value, int n_db, const int64_t *db_off,
+                      const int32_t *db_word, const double *db_value, double *score, int32_t *n_common,
+                      hipStream_t st);
+struct BowSolver;
+void bow_destroy(BowSolver *s);
+
 }  // namespace sqlm

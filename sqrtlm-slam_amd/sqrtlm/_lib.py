@@ -56,7 +56,9 @@ ORB_EXPORTS = ["sqlm_orb_extract", "sqlm_orb_get_level", "sqlm_orb_match_bf", "s
                "sqlm_orb_search_by_projection_local", "sqlm_orb_search_by_projection_last",
                "sqlm_orb_search_by_projection_sim3", "sqlm_orb_fuse", "sqlm_orb_search_by_projection_kf",
                "sqlm_orb_search_by_sim3", "sqlm_orb_search_by_bow_kf_frame", "sqlm_orb_search_by_bow_kf_kf", "sqlm_orb_search_for_triangulation",
-               "sqlm_orb_bench_extract"]
+               "sqlm_orb_bench_extract",
+               # DBoW2 vocabulary: BoW transform and batched L1 score
+               "sqlm_voc_create", "sqlm_voc_destroy", "sqlm_voc_info", "sqlm_bow_transform", "sqlm_bow_score"]
 
 
 class SqlmError(RuntimeError):
@@ -150,6 +152,16 @@ def lib() -> C.CDLL:
             L.sqlm_lidar_associate.argtypes = [P] + clouds + [C.c_double, P, P, P, P, P]
             L.sqlm_set_lidar_from_clouds.argtypes = [P, C.c_int32] + clouds + [P, C.c_double, C.c_double, P]
             L.sqlm_lidar_get_exec_info.argtypes = [P, P]
+        if hasattr(L, "sqlm_voc_create"):
+            P = C.c_void_p
+            # device, k, L, scoring, weighting, n_nodes, parent, is_word, desc, weight, out
+            L.sqlm_voc_create.argtypes = [C.c_int] * 5 + [C.c_int32, P, P, P, P, P]
+            L.sqlm_voc_destroy.argtypes = [P]
+            L.sqlm_voc_info.argtypes = [P, P]
+            # ctx, voc, n_img, feat_off, desc, levelsup, word, node, bow_off, bow_word, bow_value
+            L.sqlm_bow_transform.argtypes = [P, P, C.c_int, P, P, C.c_int, P, P, P, P, P]
+            # ctx, nq, q_word, q_value, n_db, db_off, db_word, db_value, score, n_common
+            L.sqlm_bow_score.argtypes = [P, C.c_int64, P, P, C.c_int, P, P, P, P, P]
         _lib = L
     return _lib
 

@@ -434,3 +434,172 @@ class ORBmatcher:
                                             ptr(m1), ptr(d1), ptr(m2), ptr(d2), C.c_float(s12), ptr(R), ptr(t),
                                             C.c_float(th), ptr(vpMatches12), C.byref(n)), "sqlm_orb_search_by_sim3")
         return n.value
+
+
+def load_vocabulary_text(path) -> dict:
+    """The DBoW2 text format (TemplatedVocabulary::loadFromTextFile,
+    TemplatedVocabulary.h:1374-1475): the header line ``k L scoring
+    weighting``, then one line per node after the root, ``parent is_leaf b0 ..
+    b31 weight``; a node's id is its read order (the root is node 0). Blank
+    lines are skipped. Returns the arrays of sqlm_voc_create as a dict."""
+    with open(path) as f:
+        lines = [ln for ln in f if ln.strip()]
+    if not lines:
+        raise ValueError(f"{path}: empty vocabulary file")
+    head = lines[0].split()
+    if len(head) != 4:
+        raise ValueError(f"{path}: header must be 'k L scoring weighting'")
+    k, L, scoring, weighting = (int(x) for x in head)
+    n = len(lines)  # the root has no line of its own
+    parent = np.zeros(n, np.int32)
+    is_word = np.zeros(n, np.uint8)
+    desc = np.zeros((n, 32), np.uint8)
+    weight = np.zeros(n, np.float64)
+    for i, ln in enumerate(lines[1:], 1):
+        t = ln.split()
+        if len(t) != 35:
+            raise ValueError(f"{path}: node {i}: expected 35 fields, found {len(t)}")
+        parent[i] = int(t[0])
+        is_word[i] = int(t[1]) > 0
+        desc[i] = [int(x) for x in t[2:34]]
+        weight[i] = float(t[34])
+    return dict(k=k, L=L, scoring=scoring, weighting=weighting, parent=parent, is_word=is_word, desc=desc,
+                weight=weight)
+
+
+def save_vocabulary_text(path, k, L, parent, is_word, desc, weight, scoring=0, weighting=0) -> None:
+    """Write the arrays in the DBoW2 text format; weights with repr(), so that
+    load_vocabulary_text reads back the same bits."""
+    with open(path, "w") as f:
+        f.write(f"{int(k)} {int(L)} {int(scoring)} {int(weighting)}\n")
+        for i in range(1, len(parent)):
+            f.write(f"{int(parent[i])} {int(is_word[i])} {' '.join(str(int(b)) for b in desc[i])} "
+                    f"{float(weight[i])!r}\n")
+
+
+class ORBVocabulary:
+    """ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) on
+    the GPU: ``transform`` (TemplatedVocabulary.h:1142-1212) and ``score``
+    (L1Scoring::score, ScoringObject.cpp:23-68).
+
+    Built from the arrays loadFromTextFile builds (node 0 is the root, parent[i]
+    < i, children in ascending id, words numbered in ascending node id) or from
+    a DBoW2 text file with ``load_text``. The device copy belongs to a device
+    and serves every context on it; ``upload=False`` keeps the arrays on the
+    host only (to convert or inspect a file on a machine without a GPU).
+    A BowVector is a pair (words int32 ascending, values float64)."""
+
+    def __init__(self, k, L, parent, is_word, desc, weight, scoring: int = 0, weighting: int = 0, device: int = -1,
+                 upload: bool = True):
+        self.k, self.L, self.scoring, self.weighting = int(k), int(L), int(scoring), int(weighting)
+        self.parent = np.ascontiguousarray(parent, np.int32)
+        n = len(self.parent)
+        self.is_word = np.ascontiguousarray(is_word, np.uint8)
+        self.desc = np.ascontiguousarray(desc, np.uint8).reshape(n, 32)
+        self.weight = np.ascontiguousarray(weight, np.float64)
+        if self.is_word.shape != (n,) or self.weight.shape != (n,):
+            raise ValueError("parent, is_word and weight hold one entry per node, desc 32 bytes per node")
+        self._h = C.c_void_p()
+        self._ctx = None
+        if upload:
+            check(lib().sqlm_voc_create(int(device), self.k, self.L, self.scoring, self.weighting, n, ptr(self.parent),
+                                        ptr(self.is_word), ptr(self.desc), ptr(self.weight), C.byref(self._h)),
+                  "sqlm_voc_create")
+
+    @classmethod
+    def load_text(cls, path, device: int = -1, upload: bool = True) -> "ORBVocabulary":
+        return cls(**load_vocabulary_text(path), device=device, upload=upload)
+
+    def save_text(self, path) -> None:
+        save_vocabulary_text(path, self.k, self.L, self.parent, self.is_word, self.desc, self.weight, self.scoring,
+                             self.weighting)
+
+    def close(self) -> None:
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+        if self._h:
+            lib().sqlm_voc_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def info(self) -> dict:
+        """k, L, n_nodes, n_words, max_children, max_leaf_depth, min_leaf_depth, device of the device copy."""
+        out = np.zeros(8, np.int32)
+        check(lib().sqlm_voc_info(self._h, ptr(out)), "sqlm_voc_info")
+        return dict(zip(("k", "L", "n_nodes", "n_words", "max_children", "max_leaf_depth", "min_leaf_depth", "device"),
+                        (int(v) for v in out)))
+
+    def _context(self, ctx):
+        if ctx is not None:
+            return ctx
+        if self._ctx is None:
+            self._ctx = Context(self.info()["device"])
+        return self._ctx
+
+    def _transform(self, descriptors, levelsup, ctx):
+        mats = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descriptors]
+        off = np.zeros(len(mats) + 1, np.int64)
+        off[1:] = np.cumsum([len(m) for m in mats])
+        n = int(off[-1])
+        desc = np.concatenate(mats) if n else np.zeros((1, 32), np.uint8)
+        word, node, bw = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        bv = np.zeros(max(n, 1), np.float64)
+        boff = np.zeros(len(mats) + 1, np.int64)
+        check(lib().sqlm_bow_transform(self._context(ctx)._h, self._h, len(mats), ptr(off), ptr(desc), int(levelsup),
+                                       ptr(word), ptr(node), ptr(boff), ptr(bw), ptr(bv)), "sqlm_bow_transform")
+        return off, word, node, boff, bw, bv
+
+    def transform_many(self, descriptors, levelsup: int = 4, ctx: Context | None = None):
+        """transform for a list of images in one call: a list of (words,
+        values, node_per_feature), one per image. node_per_feature is the
+        FeatureVector as BowFrame takes it (-1: a stop word's feature)."""
+        off, _, node, boff, bw, bv = self._transform(descriptors, levelsup, ctx)
+        return [(bw[boff[j]:boff[j + 1]].copy(), bv[boff[j]:boff[j + 1]].copy(), node[off[j]:off[j + 1]].copy())
+                for j in range(len(off) - 1)]
+
+    def transform(self, descriptors, levelsup: int = 4, ctx: Context | None = None):
+        """transform(features, v, fv, levelsup): (words, values, node_per_feature)."""
+        return self.transform_many([descriptors], levelsup, ctx)[0]
+
+    def words(self, descriptors, levelsup: int = 4, ctx: Context | None = None):
+        """transform(feature, id, weight, nid, levelsup) for every feature:
+        (word id, FeatureVector node), both -1 for a stop word."""
+        off, word, node, _, _, _ = self._transform([descriptors], levelsup, ctx)
+        return word[:off[-1]].copy(), node[:off[-1]].copy()
+
+    def score_many(self, query, vectors, ctx: Context | None = None):
+        """score(query, v) for every v of a list: (scores float64, n_common
+        int32); n_common is the number of words v shares with the query."""
+        qw = np.ascontiguousarray(query[0], np.int32)
+        qv = np.ascontiguousarray(query[1], np.float64)
+        if qw.shape != qv.shape or qw.ndim != 1:
+            raise ValueError("a BowVector is (words, values) of one length")
+        ws = [np.ascontiguousarray(v[0], np.int32).reshape(-1) for v in vectors]
+        vs = [np.ascontiguousarray(v[1], np.float64).reshape(-1) for v in vectors]
+        if any(len(a) != len(b) for a, b in zip(ws, vs)):
+            raise ValueError("a BowVector is (words, values) of one length")
+        off = np.zeros(len(ws) + 1, np.int64)
+        off[1:] = np.cumsum([len(w) for w in ws])
+        dw = np.concatenate(ws) if off[-1] else np.zeros(1, np.int32)
+        dv = np.concatenate(vs) if off[-1] else np.zeros(1, np.float64)
+        score = np.zeros(len(ws), np.float64)
+        nc = np.zeros(len(ws), np.int32)
+        check(lib().sqlm_bow_score(self._context(ctx)._h, len(qw), ptr(qw), ptr(qv), len(ws), ptr(off), ptr(dw), ptr(dv),
+                                   ptr(score), ptr(nc)), "sqlm_bow_score")
+        return score, nc
+
+    def score(self, v1, v2, ctx: Context | None = None) -> float:
+        """score(v1, v2) (TemplatedVocabulary.h:1217): the L1 score."""
+        return float(self.score_many(v1, [v2], ctx)[0][0])

@@ -165,6 +165,74 @@ def bow_nodes(desc, seed, absent=0.08):
     return node
 
 
+def make_vocabulary(k, L, seed, ragged=False, stop=0.0):
+    """A synthetic DBoW2 vocabulary as the arrays of sqlm_voc_create /
+    ORBVocabulary: dict(k, L, parent, is_word, desc, weight).
+
+    The root's children are random descriptors; every other node is its parent
+    with about one bit in eight flipped, so a descriptor near a leaf descends to
+    it and near ties between siblings are common. Node ids are depth-first
+    (pre-order), as a recursively built vocabulary saves them: a parent comes
+    before its children and siblings are in ascending id. Words sit at depth L
+    and weigh between 0.5 and 10; ``stop`` is the fraction of zero weights
+    (stop words). With ``ragged``, about a third of the inner nodes have fewer
+    than k children (one in ten a single child) and about one node in seven
+    above depth L is a word already."""
+    rng = np.random.default_rng(seed)
+    # breadth first, level by level; the nodes of a level are grouped by parent
+    par, desc, leaf = [np.zeros(1, np.int64)], [np.zeros((1, 32), np.uint8)], [np.zeros(1, bool)]
+    first = 0  # breadth-first index of the first node of the previous level
+    for d in range(1, L + 1):
+        inner = np.nonzero(~leaf[-1])[0]
+        cnt = np.full(len(inner), k, np.int64)
+        if ragged:
+            u = rng.random(len(inner))
+            cnt = np.where(u < 0.1, 1, np.where(u < 0.33, rng.integers(1, k + 1, len(inner)), k))
+        p = np.repeat(inner, cnt)
+        n = len(p)
+        if d == 1:
+            dd = rng.integers(0, 256, (n, 32), np.uint8)
+        else:
+            flip = (rng.integers(0, 256, (n, 32), np.uint8) & rng.integers(0, 256, (n, 32), np.uint8)
+                    & rng.integers(0, 256, (n, 32), np.uint8))
+            dd = desc[-1][p] ^ flip
+        lf = np.ones(n, bool) if d == L else (rng.random(n) < 0.15 if ragged else np.zeros(n, bool))
+        par.append(p + first)
+        desc.append(dd)
+        leaf.append(lf)
+        first += len(leaf[-2])
+    level_len = [len(x) for x in leaf]
+    parent_b = np.concatenate(par)
+    desc_b = np.concatenate(desc)
+    leaf_b = np.concatenate(leaf)
+    n = len(parent_b)
+    # pre-order ids: a node's id = its parent's + 1 + the subtree sizes of its earlier siblings
+    size = np.ones(n, np.int64)
+    starts = np.concatenate([[0], np.cumsum(level_len)])
+    for d in range(L, 0, -1):
+        s, e = starts[d], starts[d + 1]
+        size += np.bincount(parent_b[s:e], weights=size[s:e], minlength=n).astype(np.int64)
+    pre = np.zeros(n, np.int64)
+    for d in range(1, L + 1):
+        s, e = starts[d], starts[d + 1]
+        if e == s:
+            continue
+        excl = np.cumsum(size[s:e]) - size[s:e]
+        head = np.r_[True, parent_b[s + 1:e] != parent_b[s:e - 1]]
+        grp = np.maximum.accumulate(np.where(head, np.arange(e - s), 0))
+        pre[s:e] = pre[parent_b[s:e]] + 1 + excl - excl[grp]
+    parent = np.zeros(n, np.int32)
+    parent[pre] = pre[parent_b]
+    is_word = np.zeros(n, np.uint8)
+    is_word[pre] = leaf_b
+    out_desc = np.zeros((n, 32), np.uint8)
+    out_desc[pre] = desc_b
+    weight = np.where(is_word > 0, rng.uniform(0.5, 10.0, n), 0.0)
+    if stop > 0:
+        weight[(is_word > 0) & (rng.random(n) < stop)] = 0.0
+    return dict(k=int(k), L=int(L), parent=parent, is_word=is_word, desc=out_desc, weight=weight)
+
+
 def bow_points(n, seed, frac=0.7, bad=0.05, base=0):
     """GetMapPointMatches ids (-1: NULL) and isBad() flags."""
     rng = np.random.default_rng(seed + 91)
