@@ -1,8 +1,10 @@
 """The problems of tests/test_gpu_first_trial.py: name -> (builder, lambda,
 environment of the setup). All small (<= 60 keyframes, <= 4k landmarks).
 tests/test_lin_ref.py checks on the CPU that the oracle accepts the first
-trial of every one of them at its lambda, so the GPU test never meets a
-rejected step it would have to skip.
+trial of every one of them at its lambda: the first-trial tests run accepted
+first trials only. The retrial after a rejected step and the second iteration
+have their own cases (tests/retrial_cases.py) and tests
+(tests/test_retrial_ref.py on the CPU, tests/test_gpu_retrial.py on the GPU).
 """
 import numpy as np
 

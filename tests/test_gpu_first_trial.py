@@ -103,9 +103,10 @@ def _reference(name):
     return lin_ref.spreads(_problem(name), ALL_CASES[name][1], level=_level(name))
 
 
-def run_problem(ctx, prob, lam, setenv, env, level=0, set_lidar=None):
-    """One trial of `prob` on the GPU; setenv(key, value or None). set_lidar(ctx)
-    replaces the problem's own LiDAR edges after set_problem."""
+def run_problem(ctx, prob, lam, setenv, env, level=0, set_lidar=None, iterations=1):
+    """One iteration of `prob` on the GPU (tests/test_gpu_retrial.py: two);
+    setenv(key, value or None). set_lidar(ctx) replaces the problem's own LiDAR
+    edges after set_problem."""
     for k in SWITCHES:
         setenv(k, env.get(k))
     ctx.set_problem(prob)
@@ -113,7 +114,7 @@ def run_problem(ctx, prob, lam, setenv, env, level=0, set_lidar=None):
         set_lidar(ctx)
     elif prob.meta.get("lid_level") is not None:
         ctx.set_lidar_level(prob.meta["lid_level"])
-    n, st = ctx.optimize(level, 1, user_lambda=lam)
+    n, st = ctx.optimize(level, iterations, user_lambda=lam)
     g, dx = ctx.last_step()
     q, t = ctx.poses()
     return dict(n=n, st=st, g=g, dx=dx, q=q, t=t, X=ctx.points(), info=ctx.exec_info(), lay=ctx.rcs_layout())
@@ -130,11 +131,13 @@ def _maxrel(a, b):
     return float(np.abs(a - b).max() / np.abs(b).max())
 
 
-def ratios(oracle, name, run, reference=None):
+def ratios(oracle, name, run, reference=None, prob=None):
     """GPU error / reference spread per quantity (and both, for the table).
     reference: (spreads, longdouble trial, float64 trial) in place of the
-    case's own (the same problem at another lambda)."""
-    prob = _problem(name)
+    case's own (the same problem at another lambda). prob: the problem the
+    reference was made from, in place of the case's own (with reference;
+    tests/test_gpu_retrial.py)."""
+    prob = _problem(name) if prob is None else prob
     level = _level(name)
     sp, ref, f64 = reference or _reference(name)
     out = {}
