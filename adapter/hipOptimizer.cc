@@ -10,7 +10,6 @@
 // ascending mnId (g2o vertex ids mnId / mnId + maxKFid + 1), edges in
 // insertion order (point list order, then GetObservations() map order).
 #include "backend/hipOptimizer.h"
-#include "backend/g2oOptimizer.h"  // fallback for the configurations libsqrtlm does not cover
 
 #include <algorithm>
 #include <atomic>
@@ -28,6 +27,7 @@
 #include "KeyFrame.h"
 #include "Map.h"
 #include "MapPoint.h"
+#include "lidarconfig.h"
 #include "sqrtlm.h"
 #include "sqrtlm_capture.h"
 
@@ -87,6 +87,7 @@ struct SeamGraph {
   std::vector<MapPoint*> edge_mp;
   std::vector<int32_t> lid_pose;
   std::vector<double> lid_pc, lid_pw, lid_n, lid_info;
+  std::vector<uint8_t> lid_kind;  // 0 flat, 1 corner
   // reference write-back (capture mode)
   std::vector<float> res_Tcw, res_pt;
   std::vector<uint8_t> res_outlier;
@@ -144,6 +145,8 @@ struct SeamGraph {
     c.n_lid = (int64_t)lid_pose.size();
     c.lid_pose = lid_pose.data(); c.lid_pc = lid_pc.data(); c.lid_pw = lid_pw.data(); c.lid_n = lid_n.data();
     c.lid_info = lid_info.data();
+    // the kind section only where a corner pair exists: flat-only captures stay the files they were
+    c.lid_kind = std::find(lid_kind.begin(), lid_kind.end(), (uint8_t)1) != lid_kind.end() ? lid_kind.data() : nullptr;
     c.has_result = !res_Tcw.empty();
     c.res_Tcw = res_Tcw.empty() ? nullptr : res_Tcw.data();
     c.res_pt = res_pt.empty() ? nullptr : res_pt.data();
@@ -220,10 +223,13 @@ void build_lba(KeyFrame* pKF, SeamGraph& g, std::vector<KeyFrame*>& local, std::
 // within distance_sq_threshold. Same float pose path as the reference
 // (Converter::toCvMat then cv::Mat::inv()); the transform, the exact search
 // (the reference's kd-tree) and the accepted pairs' EdgeLidarFlatPoint edges
-// are libsqrtlm's (sqlm_set_lidar_from_clouds). false: the library failed.
+// are libsqrtlm's (sqlm_set_lidar_from_clouds). With using_sharp_point the
+// corner points join (:1075-1107): the flat and the corner search are one
+// sqlm_set_lidar_from_cloud_sets call, made by hipOptimizer::LidarCloudSets
+// (hipOptimizerLidar.cc) with the Twc computed here. false: the library failed.
 bool lidar_pairs(sqlm_ctx* ctx, KeyFrame* pKF, const std::vector<KeyFrame*>& local, const SeamGraph& g,
                  const std::vector<double>& q, const std::vector<double>& t, const lidarConfig* cfg) {
-  if (!cfg || !cfg->using_flat_point) return true;  // corner points: LocalBundleAdjustment routes to g2o
+  if (!cfg || (!cfg->using_flat_point && !cfg->using_sharp_point)) return true;
   auto Twc_of = [&](KeyFrame* k, float* out) {
     const int i = g.kf_index.at(k);
     float T[16];
@@ -238,6 +244,20 @@ bool lidar_pairs(sqlm_ctx* ctx, KeyFrame* pKF, const std::vector<KeyFrame*>& loc
       xyz.insert(xyz.end(), {p.x, p.y, p.z});
     }
   };
+  if (cfg->using_sharp_point) {  // EdgeLidarFlatPoint (if enabled) then EdgeLidarCornerPoint edges
+    std::vector<KeyFrame*> map_kfs;
+    std::vector<float> Twc;
+    for (KeyFrame* k : local) {
+      if (k->mnId == pKF->mnId) continue;
+      map_kfs.push_back(k);
+      Twc.resize(Twc.size() + 16);
+      Twc_of(k, &Twc[Twc.size() - 16]);
+    }
+    float own[16];
+    Twc_of(pKF, own);
+    long long n[2];
+    return hipOptimizer::LidarCloudSets(ctx, pKF, map_kfs, g.kf_index.at(pKF), Twc.data(), own, cfg, n);
+  }
   std::vector<int64_t> map_off{0};
   std::vector<float> map_xyz, map_Twc;
   for (KeyFrame* k : local) {
@@ -292,19 +312,6 @@ bool hipOptimizer::CaptureEnabled() { return capture_dir() != nullptr; }
 // ---------------------------------------------------------------- LBA
 
 void hipOptimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap, const lidarConfig* cfg) {
-  if (cfg && cfg->using_sharp_point) {
-    // EdgeLidarCornerPoint (pass 3 with using_sharp_point, lidarOdom.cc's ROS
-    // default) is not implemented by libsqrtlm: run the reference backend for
-    // this call instead of silently dropping the corner constraints
-    static bool warned = false;
-    if (!warned) {
-      std::cerr << "hipOptimizer: using_sharp_point=1 -> g2oOptimizer::LocalBundleAdjustment "
-                   "(EdgeLidarCornerPoint not implemented by libsqrtlm)" << std::endl;
-      warned = true;
-    }
-    g2oOptimizer::LocalBundleAdjustment(pKF, pbStopFlag, pMap, cfg);
-    return;
-  }
   sqlm_ctx* ctx = thread_ctx();
   if (!ctx) return;
   SeamGraph g;
@@ -339,7 +346,7 @@ void hipOptimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* p
     sqlm_set_robust(ctx, delta.data());
     if (!report(sqlm_optimize(ctx, 0, 10, 0.0, stop_ptr(pbStopFlag), &st, &n), "pass 2")) return;
   }
-  // pass 3 (:978-1114): LiDAR flat pairs at the pass-2 poses, 20 iterations
+  // pass 3 (:978-1114): LiDAR flat and corner pairs at the pass-2 poses, 20 iterations
   sqlm_get_poses(ctx, q.data(), t.data());
   if (!lidar_pairs(ctx, pKF, local, g, q, t, cfg)) return;
   if (!report(sqlm_optimize(ctx, 0, 20, 0.0, stop_ptr(pbStopFlag), &st, &n), "pass 3")) return;
@@ -478,6 +485,18 @@ void hipOptimizer::CaptureLidarFlat(const Eigen::Vector3d& pc, const Eigen::Vect
   g.lid_pw.insert(g.lid_pw.end(), {pw.x(), pw.y(), pw.z()});
   g.lid_n.insert(g.lid_n.end(), {n.x(), n.y(), n.z()});
   g.lid_info.push_back(w);
+  g.lid_kind.push_back(0);
+}
+
+void hipOptimizer::CaptureLidarCorner(const Eigen::Vector3d& pc, const Eigen::Vector3d& pw, double w) {
+  if (!t_capture || t_capture->kfs.empty() || t_capture_local.empty()) return;
+  SeamGraph& g = *t_capture;
+  g.lid_pose.push_back(g.kf_index.at(t_capture_local.front()));  // the current KF
+  g.lid_pc.insert(g.lid_pc.end(), {pc.x(), pc.y(), pc.z()});
+  g.lid_pw.insert(g.lid_pw.end(), {pw.x(), pw.y(), pw.z()});
+  g.lid_n.insert(g.lid_n.end(), {0.0, 0.0, 0.0});  // an EdgeLidarCornerPoint has no normal
+  g.lid_info.push_back(w);
+  g.lid_kind.push_back(1);
 }
 
 namespace {

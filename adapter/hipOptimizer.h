@@ -29,6 +29,7 @@
 // outside namespace ORB_SLAM2; a forward declaration inside the namespace
 // would name a different, incomplete type)
 struct lidarConfig;
+struct sqlm_ctx;
 
 namespace ORB_SLAM2 {
 
@@ -80,6 +81,15 @@ class hipOptimizer {
   // flat pair the reference's kd-tree found for pass 3.
   static void CaptureLidarFlat(const Eigen::Vector3d& p_cam, const Eigen::Vector3d& p_world,
                                const Eigen::Vector3d& normal, double weight);
+  // The same for the corner pair of g2oOptimizer.cc:1097-1103 (EdgeLidarCornerPoint).
+  static void CaptureLidarCorner(const Eigen::Vector3d& curr_point, const Eigen::Vector3d& near_point, double weight);
+  // LocalBundleAdjustment pass 3 with using_sharp_point (hipOptimizerLidar.cc):
+  // the flat set (using_flat_point) and the corner set of pKF against the
+  // clouds of map_kfs, one sqlm_set_lidar_from_cloud_sets call. map_Twc
+  // [map_kfs.size()][16] and cur_Twc [16] are the float T_wc of the pass-2
+  // poses; n_pairs receives {flat, corner}. false: the library failed.
+  static bool LidarCloudSets(sqlm_ctx* ctx, KeyFrame* pKF, const std::vector<KeyFrame*>& map_kfs, int pose_index,
+                             const float* map_Twc, const float* cur_Twc, const lidarConfig* cfg, long long n_pairs[2]);
   static bool CaptureEnabled();
 };
 

@@ -103,6 +103,14 @@ int sqlm_set_lidar(sqlm_ctx *ctx, int64_t n, const int32_t *pose, const double *
 int sqlm_set_edge_level(sqlm_ctx *ctx, const uint8_t *level);
 int sqlm_set_robust(sqlm_ctx *ctx, const double *delta);
 int sqlm_set_lidar_level(sqlm_ctx *ctx, const uint8_t *level);
+/* The kind of every LiDAR edge, kind [n_lid]: 0 EdgeLidarFlatPoint e = (T_cw p_w - p_c) . n,
+ * 1 EdgeLidarCornerPoint e = |T_cw p_w - p_c| (types_six_dof_expmap.h:237-262; its normal is
+ * ignored, as in sqlm_pose_refine_lidar); both 1-D with scalar information, no robust kernel,
+ * numeric Jacobian (central differences through oplus, delta 1e-9). NULL = every edge flat.
+ * Called after sqlm_set_lidar, like sqlm_set_lidar_level: sqlm_set_problem, sqlm_set_lidar
+ * and sqlm_set_lidar_from_clouds reset every edge to flat. A value above 1 is
+ * SQLM_ERR_INVALID_ARG, a call before a problem is set SQLM_ERR_STATE. */
+int sqlm_set_lidar_kind(sqlm_ctx *ctx, const uint8_t *kind);
 
 /* optimizer.initializeOptimization(level); optimizer.optimize(iterations).
  * user_lambda > 0 mirrors setUserLambdaInit. stop mirrors setForceStopFlag
@@ -114,7 +122,7 @@ int sqlm_optimize(sqlm_ctx *ctx, int level, int iterations, double user_lambda,
 /* The whole g2oOptimizer::LocalBundleAdjustment schedule on the set problem
  * (g2oOptimizer.cc:923-1136): pass 1 optimize(5) with the set Huber kernels;
  * unless stopped, tag chi2 > 5.991 || depth <= 0 edges to level 1, drop the
- * kernels, pass 2 optimize(10); pass 3 optimize(20) with the LiDAR edges;
+ * kernels, pass 2 optimize(10); pass 3 optimize(20) with the LiDAR edges of either kind;
  * outlier[n_obs] receives the final erase tags. *ran = 0 when the stop flag
  * was already set (the reference returns before pass 1). */
 int sqlm_local_ba(sqlm_ctx *ctx, const volatile uint8_t *stop, uint8_t *outlier,
@@ -326,6 +334,33 @@ int sqlm_set_lidar_from_clouds(sqlm_ctx *ctx, int32_t pose_index,
     int64_t n_query, const float *query_xyz, const float *query_Twc,
     const float *query_normal /*[n_query][3]*/, double info, double dist_sq_threshold, int64_t *n_pairs);
 
+/* Local BA pass 3 with both kinds of LiDAR edge (g2oOptimizer.cc:1034-1107): n_sets searches,
+ * each exactly that of sqlm_set_lidar_from_clouds (same transform, distance, tie rule and
+ * strict threshold) on its own map and queries. The context's LiDAR edges become set 0's
+ * accepted pairs in query order, then set 1's, and so on -- the reference inserts the flat
+ * edges, then the corner edges -- each with its set's kind (0 flat, 1 corner) and info;
+ * edges set before are replaced. query_normal may be NULL for a corner set. n_pairs [n_sets]
+ * (may be NULL) receives the pairs of each set. With more than one set, a set with an empty
+ * map or without queries contributes no edge and launches nothing; sqlm_lidar_get_exec_info
+ * describes the last set that launched a search. n_sets = 1 with kind 0 is
+ * sqlm_set_lidar_from_clouds. Errors as there; a kind other than 0 or 1 is
+ * SQLM_ERR_INVALID_ARG, and no set reaches the device unless all are valid. */
+typedef struct sqlm_lidar_set {
+  int32_t kind;
+  int32_t n_map_clouds;
+  const int64_t *map_off;    /* [n_map_clouds+1] */
+  const float *map_xyz;      /* [n_map][3] */
+  const float *map_Twc;      /* [n_map_clouds][16], NULL = world */
+  int64_t n_query;
+  const float *query_xyz;    /* [n_query][3] */
+  const float *query_Twc;    /* [16] */
+  const float *query_normal; /* [n_query][3] */
+  double info;
+  double dist_sq_threshold;
+} sqlm_lidar_set;
+int sqlm_set_lidar_from_cloud_sets(sqlm_ctx *ctx, int32_t pose_index, int n_sets, const sqlm_lidar_set *sets,
+                                   int64_t *n_pairs);
+
 /* What the context's last association ran (tests and tools; no reference counterpart):
  * out[0] = n_map, out[1] = n_query, out[2] = map segments searched by separate workgroups
  * (0: empty map or no query, nothing launched), out[3] = map points per LDS tile T,
@@ -339,10 +374,11 @@ int sqlm_get_points(sqlm_ctx *ctx, double *pt);
 /* e->chi2() from the last computed error (g2o semantics: may belong to a
  * rejected trial, and level-1 edges keep their pass-1 value). */
 int sqlm_get_edge_chi2(sqlm_ctx *ctx, double *chi2);
-/* The _error of every EdgeLidarFlatPoint edge from the last computed error,
+/* The _error of every LiDAR edge of either kind from the last computed error,
  * err [n_lid] in the caller's edge order (introspection for tests; no
- * reference counterpart): (T_cw p_w - p_c) . n at the state of the last trial
- * whose errors were computed, accepted or not. An edge that was inactive in
+ * reference counterpart): (T_cw p_w - p_c) . n of a flat edge, |T_cw p_w - p_c|
+ * of a corner edge, at the state of the last trial whose errors were computed,
+ * accepted or not. An edge that was inactive in
  * the last optimize() (fixed pose, other level) keeps the value of the last
  * optimize() in which it was active, 0 if there was none since the edges were
  * set -- what the oracle's lid_err holds (oracle/g2o_ref.c computes the error
@@ -435,7 +471,7 @@ int sqlm_comm_selftest(int device, const char *unique_id, int64_t count, double 
  * memory and calls fn(user, buf, count, dtype, op), which must all-reduce
  * `count` elements of `buf` in place across the ranks and return 0. Used to
  * run several ranks on one GPU (tests); production uses sqlm_ctx_set_comm.
- * LiDAR unary edges are owned by rank 0 (ignored on other ranks). */
+ * LiDAR unary edges, with their kinds, are owned by rank 0 (ignored on other ranks). */
 #define SQLM_DT_F64 0
 #define SQLM_DT_U8 1
 #define SQLM_DT_I32 2

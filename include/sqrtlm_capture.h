@@ -60,18 +60,22 @@ typedef struct sqlm_capture {
   float *obs_ur;       /* [n_obs] mvuRight (< 0: mono edge); NULL = all mono         */
   float *obs_inv_sigma2; /* [n_obs] mvInvLevelSigma2[octave]                         */
   float *obs_delta;    /* [n_obs] Huber delta as set (0 = no kernel); NULL = none    */
-  /* LiDAR flat-point pairs joined in LBA pass 3 (g2oOptimizer.cc:1034-1114),
+  /* LiDAR flat- and corner-point pairs joined in LBA pass 3 (g2oOptimizer.cc:1034-1114),
    * as the reference's kd-tree found them at the pass-2 poses */
   int64_t n_lid;
   int32_t *lid_pose;
   double *lid_pc, *lid_pw, *lid_n; /* [n_lid][3]                                     */
-  double *lid_info;    /* [n_lid] flat_optimized_weight                              */
+  double *lid_info;    /* [n_lid] flat_optimized_weight / corner_optimized_weight    */
   /* reference results (what the g2o backend wrote back), optional */
   uint8_t has_result;
   float *res_Tcw;      /* [n_pose][16]                                               */
   float *res_pt;       /* [n_pt][3]                                                  */
   uint8_t *res_outlier; /* [n_obs] LBA erase tags (chi2 > 5.991 || depth <= 0)      */
   double *res_chi2;    /* [n_obs] e->chi2() after the last pass                      */
+  /* kind of every LiDAR pair: 0 EdgeLidarFlatPoint, 1 EdgeLidarCornerPoint
+   * (g2oOptimizer.cc:1097-1103; lid_n unused, lid_info corner_optimized_weight).
+   * Optional section "LIDK": NULL / absent = every pair flat                       */
+  uint8_t *lid_kind;   /* [n_lid]                                                    */
 } sqlm_capture;
 
 /* Write / read a capture file. Read allocates every array (sqlm_capture_free

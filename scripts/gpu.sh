@@ -19,6 +19,9 @@
 #   tests PYTEST_ARGS   a pytest -m gpu selection
 #   lbatrace TAG        kernel trace of the config-2 local-BA bench, one trial
 #   cr SHAPE...         tools/cr_bench on "p n" shapes (e.g. "278 112" "7 48")
+#   lbacorner LIB...    interleaved A/B of local-BA pass 3 with LiDAR clouds,
+#                       flat and flat + corner (scripts/lba_corner_bench.py;
+#                       REPS the number of interleaved rounds, default 3)
 set -o pipefail
 OUT=${SQLM_OUT_DIR:-bench_out}
 mkdir -p $OUT
@@ -94,6 +97,12 @@ lbatrace)
     > $OUT/lbatr_$tag/bench.json 2> $OUT/lbatr_$tag/bench.err || exit 1
   tr=$(find $OUT/lbatr_$tag -name '*kernel_trace.csv' | head -1)
   python scripts/trial_trace.py "$tr" > $OUT/lbatr_$tag/trial.txt && cat $OUT/lbatr_$tag/trial.txt
+  ;;
+lbacorner)
+  # interleaved A/B of local-BA pass 3 with LiDAR clouds (flat, flat + corner) over library builds
+  timeout -k 10 ${SQLM_TEST_TIMEOUT:-840} python -u scripts/lba_corner_bench.py --libs "$@" --rounds ${REPS:-3} \
+    --out $OUT/lba_corner_bench.jsonl > $OUT/lba_corner_bench.log 2>&1 || { tail -20 $OUT/lba_corner_bench.log; exit 1; }
+  cat $OUT/lba_corner_bench.log
   ;;
 cr)
   out=$OUT/cr_bench.log

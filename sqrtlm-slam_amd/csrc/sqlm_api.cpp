@@ -212,7 +212,7 @@ int sqlm_set_problem(sqlm_ctx *c, int n_pose, const double *pose_q, const double
   c->obs_ur.clear(); c->pose_bf.clear(); c->obs_err3.clear();
   c->n_lid = 0;
   c->lid_pose.clear(); c->lid_pc.clear(); c->lid_pw.clear(); c->lid_n.clear(); c->lid_info.clear();
-  c->lid_level.clear(); c->lid_err.clear();
+  c->lid_level.clear(); c->lid_kind.clear(); c->lid_err.clear();
   c->has_problem = true;
   c->prepared = false;  // the CR layout of the previous problem no longer applies
   return SQLM_OK;
@@ -254,6 +254,7 @@ int sqlm_set_lidar(sqlm_ctx *c, int64_t n, const int32_t *pose, const double *p_
   c->lid_n.assign(normal, normal + 3 * n);
   c->lid_info.assign(info, info + n);
   c->lid_level.assign(n, 0);
+  c->lid_kind.assign(n, 0);
   c->lid_err.assign(n, 0.0);
   c->opt_done = false;
   return SQLM_OK;
@@ -270,6 +271,17 @@ int sqlm_set_lidar_level(sqlm_ctx *c, const uint8_t *level) {
   if (!c || !c->has_problem || (!level && c->n_lid)) return SQLM_ERR_INVALID_ARG;
   c->prepared = false;  // a setter changes what prepare() plans
   c->lid_level.assign(level, level + c->n_lid);
+  return SQLM_OK;
+}
+
+int sqlm_set_lidar_kind(sqlm_ctx *c, const uint8_t *kind) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  if (!c->has_problem) return SQLM_ERR_STATE;
+  for (int64_t e = 0; kind && e < c->n_lid; ++e)
+    if (kind[e] > 1) return SQLM_ERR_INVALID_ARG;
+  c->prepared = false;  // a setter changes what prepare() plans
+  if (kind) c->lid_kind.assign(kind, kind + c->n_lid);
+  else c->lid_kind.assign((size_t)c->n_lid, 0);
   return SQLM_OK;
 }
 
@@ -553,6 +565,52 @@ int sqlm_set_lidar_from_clouds(sqlm_ctx *c, int32_t pose_index, int n_map_clouds
   }
   if (n_pairs) *n_pairs = n;
   return sqlm_set_lidar(c, n, pose.data(), pc.data(), pw.data(), nm.data(), w.data());
+}
+
+int sqlm_set_lidar_from_cloud_sets(sqlm_ctx *c, int32_t pose_index, int n_sets, const sqlm_lidar_set *sets,
+                                   int64_t *n_pairs) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  if (!c->has_problem) return SQLM_ERR_STATE;
+  if (pose_index < 0 || pose_index >= c->n_pose || c->pose_fixed[pose_index]) return SQLM_ERR_INVALID_ARG;
+  if (n_sets < 0 || (n_sets && !sets)) return SQLM_ERR_INVALID_ARG;
+  std::vector<LidarArgs> args((size_t)n_sets);
+  for (int k = 0; k < n_sets; ++k) {  // every set is checked before the first one reaches the device
+    const sqlm_lidar_set &s = sets[k];
+    if (s.kind < 0 || s.kind > 1) return SQLM_ERR_INVALID_ARG;
+    lidar_pack(args[k], s.n_map_clouds, s.map_off, s.map_xyz, s.map_Twc, s.n_query, s.query_xyz, s.query_Twc,
+               s.dist_sq_threshold);
+    if (!lidar_args_ok(args[k]) || (s.kind == 0 && s.n_query > 0 && !s.query_normal)) return SQLM_ERR_INVALID_ARG;
+  }
+  // set by set, the accepted pairs in query order: the reference inserts the
+  // flat edges (g2oOptimizer.cc:1034-1070), then the corner edges (:1075-1107)
+  std::vector<int32_t> pose;
+  std::vector<double> pc, pw, nm, w;
+  std::vector<uint8_t> kind;
+  for (int k = 0; k < n_sets; ++k) {
+    const sqlm_lidar_set &s = sets[k];
+    const LidarArgs &a = args[k];
+    if (n_pairs) n_pairs[k] = 0;
+    // an empty map or no query: no edge, no launch (a lone set goes the way of sqlm_set_lidar_from_clouds)
+    if (n_sets > 1 && (a.n_query == 0 || a.map_off[a.n_map_clouds] == a.map_off[0])) continue;
+    if (int r = lidar_call(c, a)) return r;
+    const int64_t n = lidar_n_pairs(c->lidar);
+    const int32_t *pq = n ? lidar_pair_query(c->lidar) : nullptr;
+    const float *xyz = n ? lidar_nn_xyz(c->lidar) : nullptr;
+    for (int64_t j = 0; j < n; ++j) {
+      const int64_t i = pq[j];
+      for (int x = 0; x < 3; ++x) {
+        pc.push_back((double)s.query_xyz[3 * i + x]);
+        pw.push_back((double)xyz[3 * i + x]);
+        nm.push_back(s.query_normal ? (double)s.query_normal[3 * i + x] : 0.0);
+      }
+    }
+    pose.insert(pose.end(), (size_t)n, pose_index);
+    w.insert(w.end(), (size_t)n, s.info);
+    kind.insert(kind.end(), (size_t)n, (uint8_t)s.kind);
+    if (n_pairs) n_pairs[k] = n;
+  }
+  if (int r = sqlm_set_lidar(c, (int64_t)pose.size(), pose.data(), pc.data(), pw.data(), nm.data(), w.data())) return r;
+  return sqlm_set_lidar_kind(c, kind.data());
 }
 
 int sqlm_lidar_get_exec_info(sqlm_ctx *c, int out[8]) {

@@ -31,6 +31,7 @@ constexpr uint32_t kObsP = cc('O', 'B', 'S', 'P'), kObsL = cc('O', 'B', 'S', 'L'
 constexpr uint32_t kObsR = cc('O', 'B', 'S', 'R'), kObsI = cc('O', 'B', 'S', 'I'), kObsD = cc('O', 'B', 'S', 'D');
 constexpr uint32_t kLidP = cc('L', 'I', 'D', 'P'), kLidC = cc('L', 'I', 'D', 'C'), kLidW = cc('L', 'I', 'D', 'W');
 constexpr uint32_t kLidN = cc('L', 'I', 'D', 'N'), kLidI = cc('L', 'I', 'D', 'I');
+constexpr uint32_t kLidK = cc('L', 'I', 'D', 'K');  // optional: uint8 kind per LiDAR pair (absent: all flat)
 constexpr uint32_t kRTcw = cc('R', 'T', 'C', 'W'), kRPt = cc('R', 'P', 'N', 'T'), kROut = cc('R', 'O', 'U', 'T');
 constexpr uint32_t kRChi = cc('R', 'C', 'H', 'I');
 
@@ -118,6 +119,7 @@ int sqlm_capture_write(const char *path, const sqlm_capture *c) {
     w.section(kLidW, 8, 3 * L, c->lid_pw);
     w.section(kLidN, 8, 3 * L, c->lid_n);
     w.section(kLidI, 8, L, c->lid_info);
+    w.section(kLidK, 1, L, c->lid_kind);
   }
   if (c->has_result) {
     if (P) w.section(kRTcw, 4, 16 * P, c->res_Tcw);
@@ -136,7 +138,7 @@ void sqlm_capture_free(sqlm_capture *c) {
   if (!c) return;
   void *arrays[] = {c->Tcw, c->pose_fixed, c->intr, c->bf, c->kf_id, c->pt, c->mp_id, c->obs_pose, c->obs_pt,
                     c->obs_uv, c->obs_ur, c->obs_inv_sigma2, c->obs_delta, c->lid_pose, c->lid_pc, c->lid_pw,
-                    c->lid_n, c->lid_info, c->res_Tcw, c->res_pt, c->res_outlier, c->res_chi2};
+                    c->lid_n, c->lid_info, c->res_Tcw, c->res_pt, c->res_outlier, c->res_chi2, c->lid_kind};
   for (void *p : arrays) std::free(p);
   std::free(c);
 }
@@ -218,7 +220,7 @@ int sqlm_capture_read(const char *path, sqlm_capture **out) {
          take(secs, kObsD, E, &c->obs_delta);
   bad |= take(secs, kLidP, L, &c->lid_pose) | take(secs, kLidC, 3 * L, &c->lid_pc) |
          take(secs, kLidW, 3 * L, &c->lid_pw) | take(secs, kLidN, 3 * L, &c->lid_n) |
-         take(secs, kLidI, L, &c->lid_info);
+         take(secs, kLidI, L, &c->lid_info) | take(secs, kLidK, L, &c->lid_kind);
   bad |= take(secs, kRTcw, 16 * P, &c->res_Tcw) | take(secs, kRPt, 3 * N, &c->res_pt) |
          take(secs, kROut, E, &c->res_outlier) | take(secs, kRChi, E, &c->res_chi2);
   // required arrays, index ranges
@@ -229,7 +231,7 @@ int sqlm_capture_read(const char *path, sqlm_capture **out) {
   for (uint64_t e = 0; !bad && e < E; ++e)
     if (c->obs_pose[e] < 0 || c->obs_pose[e] >= c->n_pose || c->obs_pt[e] < 0 || c->obs_pt[e] >= c->n_pt) bad = 1;
   for (uint64_t e = 0; !bad && e < L; ++e)
-    if (c->lid_pose[e] < 0 || c->lid_pose[e] >= c->n_pose) bad = 1;
+    if (c->lid_pose[e] < 0 || c->lid_pose[e] >= c->n_pose || (c->lid_kind && c->lid_kind[e] > 1)) bad = 1;
   if (bad) {
     sqlm_capture_free(c);
     return SQLM_ERR_INVALID_ARG;
@@ -307,6 +309,7 @@ int sqlm_capture_replay(sqlm_ctx *ctx, const sqlm_capture *c, const volatile uin
     if (c->n_lid) {
       s = sqlm_set_lidar(ctx, c->n_lid, c->lid_pose, c->lid_pc, c->lid_pw, c->lid_n, c->lid_info);
       if (s) return s;
+      if (c->lid_kind && (s = sqlm_set_lidar_kind(ctx, c->lid_kind))) return s;
     }
     s = sqlm_local_ba(ctx, stop, outl.data(), out->stats, &out->ran);
   } else {

@@ -45,6 +45,7 @@ struct sqlm_ctx {
   std::vector<int32_t> lid_pose;
   std::vector<double> lid_pc, lid_pw, lid_n, lid_info, lid_err;
   std::vector<uint8_t> lid_level;
+  std::vector<uint8_t> lid_kind;     // 0 EdgeLidarFlatPoint, 1 EdgeLidarCornerPoint (sqlm_set_lidar_kind)
   // ---- structure of the current optimize() call ----
   sqlm::DevProblem d;
   // what the planner decided (buckets, update launch, S pattern, solver plan,

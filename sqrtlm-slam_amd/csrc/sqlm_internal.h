@@ -173,8 +173,9 @@ struct DevProblem {
   double *bp = nullptr;                     // [nP][8]
   // lidar unary edges (grouped by camera)
   int64_t nLid = 0;
+  int has_corner = 0;                       // some active LiDAR edge is a corner edge: selects the COR kernels
   int *lid_cam_ptr = nullptr;               // [nP+1]
-  double *lid_data = nullptr;               // [nLid][12] pc(3) pw(3) n(3) info pad pad
+  double *lid_data = nullptr;               // [nLid][12] pc(3) pw(3) n(3) info kind(0 flat, 1 corner) pad
   int *lid_pose = nullptr;                  // [nLid]
   double *lid_err = nullptr;                // [nLid]
   // reduced camera system, BSR upper, row i = free camera i

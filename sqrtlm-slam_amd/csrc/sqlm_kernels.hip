@@ -547,7 +547,12 @@ void launch_edge_errors(const DevProblem &d, int buf, hipStream_t st) {
 #ifndef SQLM_CAM_OCC
 #define SQLM_CAM_OCC 5
 #endif
-template <bool ST, bool LID>
+// COR: the instantiation for problems with EdgeLidarCornerPoint edges among the
+// LiDAR edges (d.has_corner); the kind of an edge (lid_data[10]) selects its
+// error and Jacobian. A problem without corner edges runs the COR = false
+// kernels, which are the code they were before the corner edge existed (the
+// kind selection in one kernel cost the flat path 2-4 % of a config-2 pass 3).
+template <bool ST, bool LID, bool COR = false>
 __global__ __launch_bounds__(256, LID ? 1 : SQLM_CAM_OCC) void k_camera_pass(DevProblem d, int spec) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const double *pose_rt_s = spec ? d.pose_rt[1] : d.pose_rt[0], *X_s = spec ? d.X[1] : d.X[0];
@@ -609,12 +614,14 @@ __global__ __launch_bounds__(256, LID ? 1 : SQLM_CAM_OCC) void k_camera_pass(Dev
       const double q[4] = {qt[0], qt[1], qt[2], qt[3]}, t3[3] = {qt[4], qt[5], qt[6]};
       for (int t = d.lid_cam_ptr[i] + lane; t < d.lid_cam_ptr[i + 1]; t += 64) {
         const double *L = d.lid_data + 12 * t;
-        const double e = lidar_error(q, t3, L, L + 3, L + 6);
+        const bool corner = COR && L[10] != 0.0;  // EdgeLidarCornerPoint (the normal is not read)
+        const double e = corner ? lidar_corner_error(q, t3, L, L + 3) : lidar_error(q, t3, L, L + 3, L + 6);
         d.lid_err[t] = e;
         const double info = L[9];
         chi += e * (info * e);
         double J[6];
-        lidar_jacobian(q, t3, L, L + 3, L + 6, J);
+        if (corner) lidar_corner_jacobian(q, t3, L, L + 3, J);
+        else lidar_jacobian(q, t3, L, L + 3, L + 6, J);
         int k = 0;
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
@@ -651,7 +658,10 @@ __global__ __launch_bounds__(256, LID ? 1 : SQLM_CAM_OCC) void k_camera_pass(Dev
 void launch_camera_pass(const DevProblem &d, hipStream_t st, bool spec) {
   if (d.nP == 0) return;
   const dim3 g((d.nP + 3) / 4);
-  if (d.nLid > 0) {
+  if (d.nLid > 0 && d.has_corner) {
+    if (d.has_stereo) hipLaunchKernelGGL((k_camera_pass<true, true, true>), g, dim3(256), 0, st, d, (int)spec);
+    else hipLaunchKernelGGL((k_camera_pass<false, true, true>), g, dim3(256), 0, st, d, (int)spec);
+  } else if (d.nLid > 0) {
     if (d.has_stereo) hipLaunchKernelGGL((k_camera_pass<true, true>), g, dim3(256), 0, st, d, (int)spec);
     else hipLaunchKernelGGL((k_camera_pass<false, true>), g, dim3(256), 0, st, d, (int)spec);
   } else {
@@ -2445,6 +2455,7 @@ void launch_landmark_update(const DevProblem &d, const Bucket &b, double lambda,
 #undef SQLM_LAUNCH
 }
 
+template <bool COR>
 __global__ __launch_bounds__(256) void k_lidar_chi2(DevProblem d) {
   __shared__ double red[4];
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2453,7 +2464,7 @@ __global__ __launch_bounds__(256) void k_lidar_chi2(DevProblem d) {
     const double *qt = d.pose_qt[1] + 8 * d.lid_pose[t];
     const double q[4] = {qt[0], qt[1], qt[2], qt[3]}, t3[3] = {qt[4], qt[5], qt[6]};
     const double *L = d.lid_data + 12 * t;
-    const double e = lidar_error(q, t3, L, L + 3, L + 6);
+    const double e = COR && L[10] != 0.0 ? lidar_corner_error(q, t3, L, L + 3) : lidar_error(q, t3, L, L + 3, L + 6);
     d.lid_err[t] = e;
     chi = e * (L[9] * e);
   }
@@ -2463,7 +2474,8 @@ __global__ __launch_bounds__(256) void k_lidar_chi2(DevProblem d) {
 
 void launch_lidar_chi2(const DevProblem &d, hipStream_t st) {
   if (d.nLid == 0) return;
-  hipLaunchKernelGGL(k_lidar_chi2, dim3((d.nLid + 255) / 256), dim3(256), 0, st, d);
+  if (d.has_corner) hipLaunchKernelGGL(k_lidar_chi2<true>, dim3((d.nLid + 255) / 256), dim3(256), 0, st, d);
+  else hipLaunchKernelGGL(k_lidar_chi2<false>, dim3((d.nLid + 255) / 256), dim3(256), 0, st, d);
 }
 
 // ---------------------------------------------------------------- reductions

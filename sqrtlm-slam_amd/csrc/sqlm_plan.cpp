@@ -960,7 +960,7 @@ void plan_lidar_groups(const GraphView &g, SetupPlan &pl) {
       for (int k = 0; k < 3; ++k) lid_data.push_back(g.lid_pw[3 * e + k]);
       for (int k = 0; k < 3; ++k) lid_data.push_back(g.lid_n[3 * e + k]);
       lid_data.push_back(g.lid_info[e]);
-      lid_data.push_back(0.0);
+      lid_data.push_back(g.lid_kind && g.lid_kind[e] ? 1.0 : 0.0);  // the edge's kind in the first pad slot
       lid_data.push_back(0.0);
     }
   }

@@ -86,6 +86,7 @@ struct GraphView {
   const int32_t *lid_pose = nullptr;
   const double *lid_pc = nullptr, *lid_pw = nullptr, *lid_n = nullptr, *lid_info = nullptr;
   const uint8_t *lid_level = nullptr;
+  const uint8_t *lid_kind = nullptr;  // 0 flat, 1 corner; null: every edge flat
   int level = 0;
 };
 

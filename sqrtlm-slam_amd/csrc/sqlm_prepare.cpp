@@ -37,6 +37,7 @@ GraphView graph_view(const sqlm_ctx *c, int level) {
   g.lid_n = c->lid_n.data();
   g.lid_info = c->lid_info.data();
   g.lid_level = c->lid_level.data();
+  g.lid_kind = c->lid_kind.data();
   g.level = level;
   return g;
 }
@@ -327,6 +328,8 @@ int upload_camera_side(sqlm_ctx *c, SmallUploads &small) {
   }
   UP(B_LIDPTR, pl.lid_ptr, d.lid_cam_ptr);
   UP(B_LIDDATA, pl.lid_data, d.lid_data);
+  d.has_corner = 0;
+  for (size_t t = 10; t < pl.lid_data.size(); t += 12) d.has_corner |= pl.lid_data[t] != 0.0;
   UP(B_LIDPOSE, pl.lid_pose, d.lid_pose);
   AL(B_LIDERR, (size_t)d.nLid, d.lid_err);
   return SQLM_OK;

@@ -47,6 +47,10 @@ EXPORTS = [
     "sqlm_lidar_associate", "sqlm_set_lidar_from_clouds", "sqlm_lidar_get_exec_info",
     # int sqlm_get_lidar_error(ctx, double *err /* [n_lid] */)
     "sqlm_get_lidar_error",
+    # int sqlm_set_lidar_kind(ctx, const uint8_t *kind /* [n_lid] 0 flat, 1 corner; NULL = flat */)
+    # int sqlm_set_lidar_from_cloud_sets(ctx, int32_t pose_index, int n_sets, const sqlm_lidar_set *sets,
+    #     int64_t *n_pairs /* [n_sets] */)
+    "sqlm_set_lidar_kind", "sqlm_set_lidar_from_cloud_sets",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -133,6 +137,15 @@ class PoseStats(C.Structure):
                     chi2_end=list(self.chi2_end), lambda_end=list(self.lambda_end))
 
 
+class LidarSet(C.Structure):
+    """sqlm_lidar_set: one map / query search of sqlm_set_lidar_from_cloud_sets."""
+    _fields_ = [
+        ("kind", C.c_int32), ("n_map_clouds", C.c_int32), ("map_off", C.c_void_p), ("map_xyz", C.c_void_p),
+        ("map_Twc", C.c_void_p), ("n_query", C.c_int64), ("query_xyz", C.c_void_p), ("query_Twc", C.c_void_p),
+        ("query_normal", C.c_void_p), ("info", C.c_double), ("dist_sq_threshold", C.c_double),
+    ]
+
+
 _lib = None
 
 
@@ -152,6 +165,10 @@ def lib() -> C.CDLL:
             L.sqlm_lidar_associate.argtypes = [P] + clouds + [C.c_double, P, P, P, P, P]
             L.sqlm_set_lidar_from_clouds.argtypes = [P, C.c_int32] + clouds + [P, C.c_double, C.c_double, P]
             L.sqlm_lidar_get_exec_info.argtypes = [P, P]
+        if hasattr(L, "sqlm_set_lidar_kind"):
+            P = C.c_void_p
+            L.sqlm_set_lidar_kind.argtypes = [P, P]
+            L.sqlm_set_lidar_from_cloud_sets.argtypes = [P, C.c_int32, C.c_int, P, P]
         if hasattr(L, "sqlm_voc_create"):
             P = C.c_void_p
             # device, k, L, scoring, weighting, n_nodes, parent, is_word, desc, weight, out

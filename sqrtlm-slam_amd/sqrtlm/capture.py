@@ -30,7 +30,7 @@ class _Cap(C.Structure):
         ("n_lid", C.c_int64), ("lid_pose", C.c_void_p), ("lid_pc", C.c_void_p), ("lid_pw", C.c_void_p),
         ("lid_n", C.c_void_p), ("lid_info", C.c_void_p),
         ("has_result", C.c_uint8), ("res_Tcw", C.c_void_p), ("res_pt", C.c_void_p), ("res_outlier", C.c_void_p),
-        ("res_chi2", C.c_void_p),
+        ("res_chi2", C.c_void_p), ("lid_kind", C.c_void_p),
     ]
 
 
@@ -51,6 +51,7 @@ _ARRAYS = [
     ("lid_n", np.float64, (3,), "n_lid"), ("lid_info", np.float64, (), "n_lid"),
     ("res_Tcw", np.float32, (4, 4), "n_pose"), ("res_pt", np.float32, (3,), "n_pt"),
     ("res_outlier", np.uint8, (), "n_obs"), ("res_chi2", np.float64, (), "n_obs"),
+    ("lid_kind", np.uint8, (), "n_lid"),
 ]
 
 
@@ -85,6 +86,7 @@ class Capture:
     res_pt: np.ndarray | None = None
     res_outlier: np.ndarray | None = None
     res_chi2: np.ndarray | None = None
+    lid_kind: np.ndarray | None = None  # 0 flat, 1 corner per LiDAR pair; None = every pair flat
     keep: list = field(default_factory=list, repr=False)
 
     @property

@@ -62,6 +62,8 @@ class Context:
         if p.n_lid:
             check(lib().sqlm_set_lidar(self._h, C.c_int64(p.n_lid), ptr(p.lid_pose), ptr(p.lid_pc), ptr(p.lid_pw),
                                        ptr(p.lid_n), ptr(p.lid_info)), "sqlm_set_lidar")
+            if np.any(p.lid_kind):  # a problem without corner edges makes the calls it always made
+                self.set_lidar_kind(p.lid_kind)
         if p.obs_ur is not None:
             check(lib().sqlm_set_stereo(self._h, ptr(p.obs_ur), ptr(p.pose_bf)), "sqlm_set_stereo")
         self.problem = p
@@ -77,6 +79,11 @@ class Context:
     def set_lidar_level(self, level: np.ndarray) -> None:
         level = np.ascontiguousarray(level, np.uint8)
         check(lib().sqlm_set_lidar_level(self._h, ptr(level)), "sqlm_set_lidar_level")
+
+    def set_lidar_kind(self, kind: np.ndarray | None) -> None:
+        """sqlm_set_lidar_kind: 0 flat, 1 corner per LiDAR edge; None = every edge flat."""
+        kind = None if kind is None else np.ascontiguousarray(kind, np.uint8)
+        check(lib().sqlm_set_lidar_kind(self._h, ptr(kind)), "sqlm_set_lidar_kind")
 
     # ------------------------------------------------------------- solve
     def optimize(self, level: int = 0, iterations: int = 10, user_lambda: float = 0.0, stop=None):
@@ -448,6 +455,31 @@ class Context:
         self.lidar_n_pairs = npairs.value
         return npairs.value
 
+    def set_lidar_from_cloud_sets(self, pose_index: int, sets) -> list:
+        """sqlm_set_lidar_from_cloud_sets: ``sets`` a list of dicts with the keys
+        kind, map_clouds, map_Twc, query_xyz, query_Twc, query_normal (None
+        allowed for a corner set), info, dist_sq_threshold. The edges of pose
+        ``pose_index`` become the accepted pairs set by set, each in query
+        order; returns the pair count of every set."""
+        arr = (_lib.LidarSet * max(len(sets), 1))()
+        keep = []  # the arrays the struct points into
+        for s, d in zip(arr, sets):
+            K, off, mxyz, mT, qxyz, qT = self._lidar_in(d["map_clouds"], d["map_Twc"], d["query_xyz"], d["query_Twc"])
+            nrm = d.get("query_normal")
+            nrm = None if nrm is None else np.ascontiguousarray(nrm, np.float32).reshape(qxyz.shape)
+            keep.append((off, mxyz, mT, qxyz, qT, nrm))
+            s.kind, s.n_map_clouds, s.n_query = int(d["kind"]), K, qxyz.shape[0]
+            s.map_off, s.map_xyz, s.map_Twc = (a if a is None else a.ctypes.data for a in (off, mxyz, mT))
+            s.query_xyz, s.query_Twc = qxyz.ctypes.data, qT.ctypes.data
+            s.query_normal = None if nrm is None else nrm.ctypes.data
+            s.info, s.dist_sq_threshold = float(d["info"]), float(d["dist_sq_threshold"])
+        npairs = np.zeros(max(len(sets), 1), np.int64)
+        check(lib().sqlm_set_lidar_from_cloud_sets(self._h, int(pose_index), len(sets), C.addressof(arr), ptr(npairs)),
+              "sqlm_set_lidar_from_cloud_sets")
+        out = [int(n) for n in npairs[:len(sets)]]
+        self.lidar_n_pairs = sum(out)
+        return out
+
     def lidar_exec_info(self) -> dict:
         """What the last association ran (sqlm_lidar_get_exec_info)."""
         out = (C.c_int * 8)()
@@ -564,10 +596,13 @@ class Optimizer:
         q, t = c.poses()  # :978-1073 at the pass-2 estimates
         Twc = [_l.Twc_f32(q[p], t[p]) for p in clouds.pose_index]
         oth = clouds.others
-        c.set_lidar_from_clouds(int(clouds.pose_index[clouds.current]), [clouds.xyz[k] for k in oth],
-                                np.stack([Twc[k] for k in oth]) if oth else np.zeros((0, 16), np.float32),
-                                clouds.query_xyz, Twc[clouds.current], clouds.query_normal, clouds.weight,
-                                clouds.dist_sq_threshold)
+        if clouds.corner_xyz is not None:  # flat then corner edges (:1034-1107), one call
+            c.set_lidar_from_cloud_sets(int(clouds.pose_index[clouds.current]), clouds.cloud_sets(Twc))
+        else:
+            c.set_lidar_from_clouds(int(clouds.pose_index[clouds.current]), [clouds.xyz[k] for k in oth],
+                                    np.stack([Twc[k] for k in oth]) if oth else np.zeros((0, 16), np.float32),
+                                    clouds.query_xyz, Twc[clouds.current], clouds.query_normal, clouds.weight,
+                                    clouds.dist_sq_threshold)
         _, st[2] = c.optimize(0, 20, 0.0, stop)  # :1113-1114
         outl = cls._tagged(c, prob).astype(np.uint8)  # :1119-1136
         cls._write_back(c, prob)

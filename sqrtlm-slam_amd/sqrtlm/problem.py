@@ -9,7 +9,8 @@ assemble (src/backend/g2oOptimizer.cc:805-912, :142-296):
 * points  -> ``VertexSBAPointXYZ`` (always marginalised);
 * obs     -> ``EdgeSE3ProjectXYZ`` in insertion order (pose, point, uv,
   ``invSigma2`` information, Huber delta or 0 for "no kernel", level);
-* lidar   -> ``EdgeLidarFlatPoint`` unary pose edges (g2oOptimizer.cc:1062-1070);
+* lidar   -> ``EdgeLidarFlatPoint`` unary pose edges (g2oOptimizer.cc:1062-1070) and, where
+  ``lid_kind`` is 1, ``EdgeLidarCornerPoint`` ones (:1097-1103; ``lid_n`` unused);
 * stereo  -> an observation with ``obs_ur >= 0`` is an ``EdgeStereoSE3ProjectXYZ``
   (u, v, u_right; ``bf`` of its keyframe), the GBA stereo branch
   (g2oOptimizer.cc:247-281); ``obs_ur = None`` means every edge is mono.
@@ -47,6 +48,7 @@ class BAProblem:
     lid_pw: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
     lid_n: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
     lid_info: np.ndarray = field(default_factory=lambda: np.zeros(0))
+    lid_kind: np.ndarray | None = None  # (K,) uint8, 0 flat 1 corner; None = every edge flat
     obs_ur: np.ndarray | None = None    # (E,) float64, < 0 = mono edge
     pose_bf: np.ndarray | None = None   # (P,) float64 mbf (stereo edges)
     meta: dict = field(default_factory=dict)
@@ -68,6 +70,9 @@ class BAProblem:
         self.lid_pw = np.ascontiguousarray(self.lid_pw, np.float64).reshape(-1, 3)
         self.lid_n = np.ascontiguousarray(self.lid_n, np.float64).reshape(-1, 3)
         self.lid_info = np.ascontiguousarray(self.lid_info, np.float64).reshape(-1)
+        if self.lid_kind is None:
+            self.lid_kind = np.zeros(self.lid_pose.shape[0], np.uint8)
+        self.lid_kind = np.ascontiguousarray(self.lid_kind, np.uint8).reshape(-1)
         if self.obs_ur is not None:
             self.obs_ur = np.ascontiguousarray(self.obs_ur, np.float64).reshape(-1)
             if self.pose_bf is None:
@@ -108,6 +113,11 @@ class BAProblem:
                 raise ValueError(f"{name} has wrong length")
         if K and (self.lid_pose.min() < 0 or self.lid_pose.max() >= P):
             raise ValueError("lid_pose out of range")
+        # code that replaces the other lid_* arrays without naming the kinds means flat edges
+        if not np.any(self.lid_kind) and self.lid_kind.shape[0] != K:
+            self.lid_kind = np.zeros(K, np.uint8)
+        if self.lid_kind.shape[0] != K or (K and self.lid_kind.max() > 1):
+            raise ValueError("lid_kind has wrong length or a value above 1")
         if self.obs_ur is not None and self.obs_ur.shape[0] != E:
             raise ValueError("obs_ur has wrong length")
         if self.pose_bf is not None and self.pose_bf.shape[0] != P:

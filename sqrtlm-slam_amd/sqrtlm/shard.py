@@ -40,8 +40,8 @@ def shard_by_owner(prob: BAProblem, owner, rank: int) -> BAProblem:
     """The sub-problem of rank `rank` under the owner map `owner[n_pt]` (the
     rank of every landmark): all poses, its landmarks in their original order
     (re-indexed from 0), their observations in their original relative order,
-    stereo arrays carried; the LiDAR edges and ``meta["lid_level"]`` on rank 0
-    only."""
+    stereo arrays carried; the LiDAR edges, their kinds and
+    ``meta["lid_level"]`` on rank 0 only."""
     owner = np.asarray(owner).reshape(-1)
     if owner.shape[0] != prob.n_pt:
         raise ValueError("owner needs one rank per landmark")
@@ -51,7 +51,7 @@ def shard_by_owner(prob: BAProblem, owner, rank: int) -> BAProblem:
     lid, meta = {}, {}
     if rank == 0 and prob.n_lid:
         lid = dict(lid_pose=prob.lid_pose, lid_pc=prob.lid_pc, lid_pw=prob.lid_pw, lid_n=prob.lid_n,
-                   lid_info=prob.lid_info)
+                   lid_info=prob.lid_info, lid_kind=prob.lid_kind)
         if prob.meta.get("lid_level") is not None:
             meta = dict(lid_level=prob.meta["lid_level"])
     stereo = {}

@@ -598,6 +598,12 @@ def make_lidar_clouds(*args, **kw):
     return make(*args, **kw)
 
 
+def make_lidar_corner_clouds(*args, **kw):
+    """A scene of line segments seen from K poses as LiDAR corner clouds: see lidar.make_corner_clouds."""
+    from .lidar import make_corner_clouds as make
+    return make(*args, **kw)
+
+
 # ---- synthetic grey images for the ORB front end (SURVEY.md §8 f3) ----------
 
 def make_scene(w: int, h: int, *, seed: int = 0, n_rect: int = 0, n_disk: int = 0) -> np.ndarray:
