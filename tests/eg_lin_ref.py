@@ -17,7 +17,12 @@ everything after them in the number type it is given:
   H_ij += A^T Omega B (and its transpose), b_i -= A^T Omega e,
   b_j -= B^T Omega e;
 * (H + lam I) dx = b solved densely (lin_ref._solve_refined);
-* chi2 = sum e^T Omega e at any state (e from the oracle at that state).
+* chi2 = sum e^T Omega e at any state (e from the oracle at that state);
+* the LM control of a trial (tests/test_eg_gpu_retrial.py): its gain ratio rho
+  and the lambda an accepted trial leaves (levenberg.cpp:118-139).
+
+first_trial() is a trial at any state: edge_data() on a graph at that state
+(eg_retrial_cases.state_graph).
 """
 from __future__ import annotations
 
@@ -154,6 +159,33 @@ def spreads(oracle, pg, lam, ed: EdgeData | None = None):
     out = dict(b=_rel(f64.b, ref.b), dx=_rel(f64.dx, ref.dx), pose=pose_err(S_lo, S_hi),
                chi2_0=_rel(f64.chi2_0, ref.chi2_0))
     return out, ref, f64, S_hi, S_lo
+
+
+def rho(chi2_0, chi2_1, dx, b, lam):
+    """The gain ratio of a trial as the LM loop forms it (levenberg.cpp:118-125
+    with computeScale): (chi2_0 - chi2_1) / (sum dx (lam dx + b) + 1e-3), in
+    the number type of dx. b is the undamped right-hand side."""
+    T = dx.dtype.type
+    dx, b = np.asarray(dx).reshape(-1), np.asarray(b).astype(dx.dtype).reshape(-1)
+    scale = (dx * (T(lam) * dx + b)).sum() + T(1e-3)
+    return (T(chi2_0) - T(chi2_1)) / scale
+
+
+def lambda_accepted(lam, rho):
+    """The damping after an accepted trial (levenberg.cpp:136-139):
+    lam max(1/3, min(1 - (2 rho - 1)^3, 2/3)), in the number type of rho."""
+    T = type(rho)
+    alpha = min(T(1) - (T(2) * rho - T(1)) ** 3, T(2) / T(3))
+    return T(lam) * max(T(1) / T(3), alpha)
+
+
+def trial_rho(oracle, pg, tr: Trial, lam, dtype=LD):
+    """(rho, chi2 at the trial state, trial state) of the trial `tr` made at
+    pg.Siw with damping lam: the step applied through the oracle's float64
+    oplus, the errors there from the oracle, chi2 and rho in `dtype`."""
+    S1 = oplus_poses(oracle, pg, tr.free, tr.dx.astype(np.float64))
+    c1 = chi2(oracle, pg, S1, dtype)
+    return rho(tr.chi2_0, c1, tr.dx.astype(dtype), tr.b, lam), c1, S1
 
 
 def chi2_spread(oracle, pg, Siw):

@@ -104,14 +104,15 @@ def _reference(oracle, name):
     return _refs[name]
 
 
-def layouts_of(name):
-    """The layouts the case admits that differ from its default."""
-    solve = EXPECT[GRAPH_OF[name]]["solve"]
+def layouts_of(name, expect=None):
+    """The layouts the case admits that differ from its default (expect: the
+    default layout's exec info, EXPECT's entry of the case's graph)."""
+    solve = (expect or EXPECT[GRAPH_OF[name]])["solve"]
     return ["default"] + {"cr": ["cholesky", "dense"], "arrow_cholesky": ["dense"], "dense": []}[solve]
 
 
-def expected_info(name, layout):
-    exp = dict(EXPECT[GRAPH_OF[name]])
+def expected_info(name, layout, expect=None):
+    exp = dict(expect or EXPECT[GRAPH_OF[name]])
     if layout == "cholesky":
         exp.update(solve="arrow_cholesky", nc=0, R=0, n_last=0)
     elif layout == "dense":
@@ -119,14 +120,17 @@ def expected_info(name, layout):
     return exp
 
 
-def run_gpu(ctx, name, monkeypatch, layout="default"):
-    pg = _graph(name)
+def run_gpu(ctx, name, monkeypatch, layout="default", pg=None, lam=None, iterations=1):
+    """eg_optimize(iterations, lam) on pg under the layout's switches; the
+    case's own graph and lambda unless given (tests/test_eg_gpu_retrial.py
+    gives its own)."""
+    pg = _graph(name) if pg is None else pg
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in LAYOUTS[layout].items():
         monkeypatch.setenv(k, v)
     ctx.eg_set_problem(pg)
-    n, st = ctx.eg_optimize(1, CASES[name][1])
+    n, st = ctx.eg_optimize(iterations, CASES[name][1] if lam is None else lam)
     b, dx = ctx.eg_last_step()
     return dict(n=n, st=st, b=b, dx=dx, S=ctx.eg_poses(), edge_chi2=ctx.eg_edge_chi2(), info=ctx.eg_exec_info())
 
@@ -136,10 +140,12 @@ def _maxrel(a, b):
     return float(np.abs(a - b).max() / np.abs(b).max())
 
 
-def ratios(oracle, name, run):
-    """name -> (GPU error / max(spread, floor), error, spread) per quantity."""
-    pg = _graph(name)
-    sp, ref, f64, S_hi, S_lo = _reference(oracle, name)
+def ratios(oracle, name, run, pg=None, reference=None):
+    """name -> (GPU error / max(spread, floor), error, spread) per quantity.
+    pg and reference (eg_lin_ref.spreads() of the trial compared) default to
+    the case's own; the trial chi2 compared is the run's last trace entry."""
+    pg = _graph(name) if pg is None else pg
+    sp, ref, f64, S_hi, S_lo = _reference(oracle, name) if reference is None else reference
     out = {}
 
     def put(key, err, spread):
@@ -153,7 +159,7 @@ def ratios(oracle, name, run):
     act, e = eg_lin_ref.edge_errors(oracle, pg, run["S"])
     c_hi = eg_lin_ref.edge_chi2(pg, act, e, LD)
     c_lo = eg_lin_ref.edge_chi2(pg, act, e, np.float64)
-    put("chi2", float(abs(LD(run["st"]["trace_chi2"][0]) - c_hi.sum()) / c_hi.sum()),
+    put("chi2", float(abs(LD(run["st"]["trace_chi2"][-1]) - c_hi.sum()) / c_hi.sum()),
         float(abs(LD(c_lo.sum()) - c_hi.sum()) / c_hi.sum()))
     put("edge_chi2", _maxrel(run["edge_chi2"][act], c_hi), _maxrel(c_lo, c_hi))
     return out
@@ -165,10 +171,10 @@ def _one_accepted_trial(run):
     assert run["st"]["trials"] == 1
 
 
-def _check_path(name, layout, run):
-    pg = _graph(name)
+def _check_path(name, layout, run, pg=None, expect=None):
+    pg = _graph(name) if pg is None else pg
     act, free, _ = eg_lin_ref.active(pg)
-    exp = expected_info(name, layout)
+    exp = expected_info(name, layout, expect)
     got = {k: run["info"][k] for k in exp}
     assert got == exp, (name, layout, run["info"])
     assert run["info"]["n_free"] == free.size and run["st"]["n_active_edges"] == act.size
