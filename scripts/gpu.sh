@@ -15,7 +15,10 @@
 #   ab LIB[:VAR=V]...   interleaved config-4 A/B of library builds
 #                       (scripts/ab_bench.py; AB_ARGS passes bench arguments,
 #                       REPS the number of interleaved rounds, default 3)
-#   bits LIB [SCALE]    bitwise A/B of a library build against the in-tree one
+#   bits LIB [SCALE] [--first-trial]
+#                       bitwise A/B of a library build against the in-tree one
+#                       (--first-trial: also one trial of every case of
+#                       tests/first_trial_cases.py; the whole log is $OUT/ab_bits.log)
 #   tests PYTEST_ARGS   a pytest -m gpu selection
 #   lbatrace TAG        kernel trace of the config-2 local-BA bench, one trial
 #   cr SHAPE...         tools/cr_bench on "p n" shapes (e.g. "278 112" "7 48")

@@ -688,7 +688,7 @@ int sqlm_get_exec_info(sqlm_ctx *c, int out[8]) {
   out[0] = c->d.obs_f32 ? 1 : 0;
   out[1] = c->d.nP == 0 ? 0 : !pl.enabled ? 4 : pl.R ? 3 : 1;
   const DevProblem &d = c->d;
-  out[2] = d.nP == 0 ? 0 : !c->use_tiles ? 1 : rcs_tile_kernel(d);
+  out[2] = d.nP == 0 ? kTileKernelNone : !c->use_tiles ? kTileKernelRows : rcs_tile_kernel(d);
   if (c->use_tiles && d.n_tiles > 0)
     for (int nt = 0; nt <= kTileNtMax; ++nt)
       if (d.tile_cls_cnt[nt] > 0) out[3] |= 1 << nt;

@@ -58,7 +58,6 @@ struct sqlm_ctx {
   int n_active_edges = 0;
   int n_cu = 0;
   bool use_tiles = false;
-  int tile_max_cp = 0, tile_max_k = 0;
   // the last optimize()'s per-edge errors are still on the device only
   // (fetched when an edge chi2 is asked for, or before the next prepare())
   bool err_pending = false;

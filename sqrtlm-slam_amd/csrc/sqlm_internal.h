@@ -356,10 +356,16 @@ struct TileStreams {
   hipStream_t s[2] = {nullptr, nullptr};
   hipEvent_t fork = nullptr, join[2] = {nullptr, nullptr};
 };
-void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k, hipStream_t st,
-                      const TileStreams *ts = nullptr);
-// the kernel launch_rcs_tiles picks for d's tiles, in sqlm_get_exec_info's
-// numbering: 0 no tile, 2 k_rcs_tile mono, 3 k_rcs_tile stereo, 4 k_rcs_tile_p
+void launch_rcs_tiles(const DevProblem &d, double lambda, hipStream_t st, const TileStreams *ts = nullptr);
+// the RCS kernel of a problem, in sqlm_get_exec_info's numbering (include/sqrtlm.h)
+enum TileKernel {
+  kTileKernelNone = 0,      // no free pose / no tile
+  kTileKernelRows = 1,      // k_rcs, the row fallback (no tile plan)
+  kTileKernelMono = 2,      // k_rcs_tile<NT, false>
+  kTileKernelStereo = 3,    // k_rcs_tile<NT, true>
+  kTileKernelProducer = 4,  // k_rcs_tile_p<NT>
+};
+// the kernel launch_rcs_tiles picks for d's tiles (a TileKernel; never kTileKernelRows)
 int rcs_tile_kernel(const DevProblem &d);
 void launch_rcs_reduce(const DevProblem &d, double lambda, hipStream_t st);
 #ifdef SQLM_TILE_PROF

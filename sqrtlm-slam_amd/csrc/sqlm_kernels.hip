@@ -11,13 +11,27 @@
 //   --- per LM trial ---
 //   k_damp             Givens-damp R with sqrt(lambda) I -> M = (H_ll+lambda)^-1
 //                      [setLambda + D->inverse(), block_solver.hpp:564-589, :389]
-//   k_rcs              reduced camera system rows S_i*, g_i
-//                      [Schur loop, block_solver.hpp:381-439]
-//   launch_dense_solve S dx = g  [LinearSolverEigen::solve] when S is not banded
+//   k_rcs_tile<NT,ST>  reduced camera system [Schur loop, block_solver.hpp:381-439]
+//   k_rcs_tile_p<NT>   as per-tile partials of S and g on the FP64 matrix
+//                      cores, one launch per accumulator-width class NT:
+//                      k_rcs_tile_p (producer / consumer waves) for mono
+//                      problems, the four-wave k_rcs_tile for stereo, repeated
+//                      cameras, long tracks and SQLM_TILE_PROD=0
+//   k_rcs_reduce       S, g = fixed-order sums of the tile partials + H_pp +
+//                      lambda I, b_p, written into the solver's layout
+//   k_rcs              row fallback (a window wider than kTileHardCams
+//                      cameras): rows S_i*, g_i directly, no partials
+//   launch_cr_solve    S dx = g [LinearSolverEigen::solve] by block cyclic
+//                      reduction of the banded (+ border) S: sqlm_rcs_solve.hip
+//   launch_dense_solve the same on a dense S when it is not banded
 //   k_pose_update      T <- exp(dx) T, pose part of computeScale
-//   k_landmark_update<W> back-substitution, X += dl, new residuals + chi2
+//   k_landmark_update_all  every bucket in one launch: back-substitution,
+//                      X += dl, new residuals + chi2 (k_landmark_update<W>:
+//                      one bucket, the fused first bucket of small problems)
 //                      [block_solver.hpp:459-483, sparse_optimizer.cpp:422-435]
 //   k_reduce           deterministic fixed-order sums of the block partials
+//   --- on request ---
+//   k_edge_errors      per-edge _error at a state buffer (the loop keeps none)
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -1013,7 +1027,16 @@ constexpr int kTileBL = 4, kTileKS = (3 * kTileBL + 3) / 4, kTileRows = 4 * kTil
 // kTileThreads / kTileBL = 64 observations and no camera seen twice by a landmark
 constexpr int kTileFastK = kTileThreads / kTileBL;
 
-// MFMA phase of one batch for the accumulator tiles q = P (mod kTileWaves):
+// ---- the pieces k_rcs_tile and k_rcs_tile_p share ----
+// One copy of everything both tile kernels compute, inlined into each: the
+// two kernels' partials are bitwise identical because every product and sum
+// below is the same code (the file is built with the default FMA contraction,
+// so a second copy of an expression is a second chance to contract it
+// differently). The LDS arrays are declared by the kernels and passed in.
+
+// MFMA phase of one batch for the accumulator tiles q = P (mod W), W the
+// number of waves that own tiles (k_rcs_tile: all kTileWaves, k_rcs_tile_p: its
+// kTileCons consumers):
 // acc[q/W] += sum_ks Y[4ks..4ks+3][ti-tile]^T Y[4ks..4ks+3][tj-tile].
 // Both operands of every MFMA are entries Y[4ks + (lane>>4)][16t + (lane&15)],
 // so the lane's NT x 4 values are read from LDS once and the MFMAs then issue
@@ -1021,38 +1044,141 @@ constexpr int kTileFastK = kTileThreads / kTileBL;
 // The pair loop runs over the union span [tmin, tmax] of the batch with all K
 // steps branch-free (per-landmark spans would save MFMAs but split the chain
 // into basic blocks the compiler cannot interleave: measured slower).
-template <int NT, int P, int NC>
+// KSTEP (k_rcs_tile_p's wide classes only) takes one K step at a time: its NT
+// operand tiles in registers, then every owned pair of the span. Each
+// accumulator still adds its K steps in order, so the sums are the same bits,
+// with a third of the operand registers.
+template <int NT, int W, int P, bool KSTEP, int NC>
 __device__ __forceinline__ void tile_mfma(d4v *acc, const double (*Y)[NC], int tmin, int tmax, int nks, int r16,
                                           int k4) {
-  double op[NT][kTileKS];
+  constexpr int NK = KSTEP ? 1 : kTileKS;  // K steps whose operands are in registers at once
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
+  for (int k0 = 0; k0 < kTileKS; k0 += NK) {
+    if (KSTEP && k0 >= nks) continue;
+    double op[NT][NK];
 #pragma unroll
-    for (int ks = 0; ks < kTileKS; ++ks) op[t][ks] = Y[4 * ks + k4][t * 16 + r16];
-  int q = 0;
+    for (int t = 0; t < NT; ++t)
 #pragma unroll
-  for (int ti = 0; ti < NT; ++ti) {
+      for (int ks = 0; ks < NK; ++ks) op[t][ks] = Y[4 * (k0 + ks) + k4][t * 16 + r16];
+    int q = 0;
 #pragma unroll
-    for (int tj = ti; tj < NT; ++tj, ++q) {
-      if (q % kTileWaves == P && ti >= tmin && tj <= tmax) {
+    for (int ti = 0; ti < NT; ++ti) {
 #pragma unroll
-        for (int ks = 0; ks < kTileKS; ++ks)
-          if (ks < nks)
-            acc[q / kTileWaves] =
-                __builtin_amdgcn_mfma_f64_16x16x4f64(op[ti][ks], op[tj][ks], acc[q / kTileWaves], 0, 0, 0);
+      for (int tj = ti; tj < NT; ++tj, ++q) {
+        if (q % W == P && ti >= tmin && tj <= tmax) {
+#pragma unroll
+          for (int ks = 0; ks < NK; ++ks)
+            if (KSTEP || k0 + ks < nks)
+              acc[q / W] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ti][ks], op[tj][ks], acc[q / W], 0, 0, 0);
+        }
       }
     }
   }
 }
 
-// tile_mfma for this wave's accumulator tiles (P = wave, a compile-time constant)
+// k_rcs_tile: tile_mfma for this wave's accumulator tiles (P = wave, a compile-time constant)
 template <int NT, int P = 0, int NC>
 __device__ __forceinline__ void tile_mfma_wave(int wave, d4v *acc, const double (*Y)[NC], int tmin, int tmax, int nks,
                                                int r16, int k4) {
   if constexpr (P + 1 < kTileWaves) {
     if (wave != P) return tile_mfma_wave<NT, P + 1>(wave, acc, Y, tmin, tmax, nks, r16, k4);
   }
-  tile_mfma<NT, P>(acc, Y, tmin, tmax, nks, r16, k4);
+  tile_mfma<NT, kTileWaves, P, false>(acc, Y, tmin, tmax, nks, r16, k4);
+}
+
+// Start of a tile, all threads: clears both Y buffers and loads the tile's
+// per-landmark data once -- Lb observation offsets, Lr / Lw = the damped
+// R'^-1 and w, Lx the landmarks at the linearization point, Lc the window
+// cameras (R t fx fy cx cy; Lbf their bf, stereo only) and Bs the column span
+// (cmin, cmax) of every batch. The caller's barrier follows.
+template <bool ST, int NC>
+__device__ __forceinline__ void tile_preamble(const DevProblem &d, int t, int cp, int l0, int ntl, int nbatch,
+                                              double lambda, int tid, double (*Ys)[kTileRows][NC], int *Lb,
+                                              double (*Lw)[3], double (*Lr)[6], double (*Lx)[3], double (*Lc)[16],
+                                              double *Lbf, int2 *Bs) {
+  constexpr int TH = kTileThreads, BL = kTileBL;
+  for (int k = tid; k < 2 * kTileRows * NC; k += TH) (&Ys[0][0][0])[k] = 0.0;
+  for (int k = tid; k <= ntl; k += TH) Lb[k] = d.lm_begin[l0 + k];
+  for (int li = tid; li < ntl; li += TH) damp_factor(d.lm_R + 8 * (l0 + li), d.lm_b + 4 * (l0 + li), lambda, Lr[li], Lw[li]);
+  for (int k = tid; k < 3 * ntl; k += TH) {
+    const int li = k / 3, c = k - 3 * li;
+    Lx[li][c] = d.X[0][4 * (l0 + li) + c];
+  }
+  {
+    const int cb = d.tile_cam_ptr[t];
+    for (int k = tid; k < 16 * cp; k += TH) {
+      const int u = k >> 4, c = k & 15;
+      Lc[u][c] = d.pose_rt[0][16 * d.hidx_pose[d.tile_cams[cb + u]] + c];
+    }
+    if (ST)
+      for (int u = tid; u < cp; u += TH) Lbf[u] = d.pose_bf[d.hidx_pose[d.tile_cams[cb + u]]];
+  }
+  for (int bt = tid; bt < nbatch; bt += TH) {  // batch spans from the landmarks' camera ranges
+    int cmin = 1 << 30, cmax = -1;
+    for (int li = BL * bt; li < min(BL * bt + BL, ntl); ++li) {
+      const int2 ur = d.lm_urange[l0 + li];
+      if (ur.x >= 0) { cmin = min(cmin, 6 * ur.x); cmax = max(cmax, 6 * ur.y + 6); }
+    }
+    Bs[bt] = int2{cmin, cmax};
+  }
+}
+
+// cr_direct: tile t's share of clearing the CR superblocks that k_rcs_reduce fills next
+__device__ __forceinline__ void tile_cr_clear(const DevProblem &d, int t, int tid) {
+  if (!d.cr_direct) return;
+  const int64_t tot = (int64_t)d.cr_p * d.cr_n * d.cr_n;  // doubles per array (even: n % 16 == 0)
+  const int64_t per = ((tot + d.n_tiles - 1) / d.n_tiles + 1) & ~(int64_t)1;
+  const int64_t a0 = (int64_t)t * per, a1 = min(tot, a0 + per);
+  for (int64_t k = a0 + 2 * tid; k < a1; k += 2 * kTileThreads) {
+    store2(d.cr_D + k, 0.0, 0.0);
+    store2(d.cr_E + k, 0.0, 0.0);
+  }
+}
+
+// Landmark li of a staged batch in gradient column gcol: Y_l[:, gcol]^T w_l.
+// A thread's column of a batch is the sum of these over the batch's landmarks
+// in order, subtracted from its gacc. (The loop stays with the two callers:
+// inside this function it cost k_rcs_tile_p<8> two VGPRs and with them 36 B
+// of scratch per lane.)
+template <int NC>
+__device__ __forceinline__ double tile_grad_term(const double (*Y)[NC], const double *w, int li, int gcol) {
+  return Y[3 * li][gcol] * w[0] + Y[3 * li + 1][gcol] * w[1] + Y[3 * li + 2][gcol] * w[2];
+}
+
+// End of a tile, for the wave that owns the accumulator tiles q = owner (mod W):
+// write -G_t as the tile's partial, block-major (tile_blk): element (R, C) of
+// an upper 16x16 tile goes to block (R/6, C/6) if that block is upper; a
+// diagonal block straddling two tiles also gets the mirror of the elements
+// whose transpose falls in the (never computed) lower tile. Then the thread's
+// gradient column (gcol = tid - 64, waves 1.. of either kernel).
+template <int NT, int W>
+__device__ __forceinline__ void tile_write_partial(const DevProblem &d, int t, int cp, int owner, const d4v *acc,
+                                                   double gacc, int tid) {
+  const int lane = tid & 63, r16 = lane & 15, k4 = lane >> 4, gcol = tid - 64;
+  const int ncol = 6 * cp, nt = (ncol + 15) >> 4;
+  double *out = d.part + d.tile_part_ptr[t];
+  const int n6 = 6 * cp;
+  int q = 0;
+#pragma unroll
+  for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+    for (int tj = ti; tj < NT; ++tj, ++q) {
+      if (q % W == owner && tj < nt) {
+        const int C = tj * 16 + r16, w = C / 6, c = C - 6 * w;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int R = ti * 16 + k4 + 4 * j, u = R / 6, r = R - 6 * u;
+          if (R < n6 && C < n6 && u <= w) {
+            double *blk = out + 36 * tile_blk(u, w, cp);
+            const double v = -acc[q / W][j];
+            blk[6 * r + c] = v;
+            if (u == w && ti < tj) blk[6 * c + r] = v;
+          }
+        }
+      }
+    }
+  double *go = d.gpart + d.tile_gpart_ptr[t];
+  if (gcol >= 0 && gcol < ncol) go[gcol] = gacc;
 }
 
 // Y block of one mono observation into rows Y[0..2] (row stride ld) at
@@ -1124,9 +1250,8 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
   constexpr int NC = NT * 16;
   constexpr int BL = kTileBL;
   __shared__ double Ys[2][kTileRows][NC];
-  // per-landmark data of the whole tile, loaded once: offsets, camera span, w, R'^-1
+  // per-landmark data of the whole tile, loaded once (tile_preamble): offsets, w, R'^-1
   __shared__ int Lb[kTileMaxLm + 1];
-  __shared__ int2 Lu[kTileMaxLm];
   __shared__ double Lw[kTileMaxLm][3];
   __shared__ double Lr[kTileMaxLm][6];
   __shared__ double Lx[kTileMaxLm][3];            // landmarks at the linearization point
@@ -1135,7 +1260,6 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
   __shared__ int2 Bs[(kTileMaxLm + kTileBL - 1) / kTileBL];  // column span of every batch (cmin, cmax)
   const int t = d.tile_order[cls_off + blockIdx.x], tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int cp = d.tile_cam_ptr[t + 1] - d.tile_cam_ptr[t];
-  const int ncol = 6 * cp, nt = (ncol + 15) >> 4;
   const int r16 = lane & 15, k4 = lane >> 4;
   d4v acc[NQW];
 #pragma unroll
@@ -1145,34 +1269,10 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
   static_assert(NT * 16 <= kTileThreads - 64, "one gradient column per thread of waves 1..");
   const int gcol = tid - 64;
   double gacc = 0.0;
-  for (int k = tid; k < 2 * kTileRows * NC; k += TH) (&Ys[0][0][0])[k] = 0.0;
   const int l0 = d.tile_lm_ptr[t], l1 = d.tile_lm_ptr[t + 1], ntl = l1 - l0;
   const int nbatch = (ntl + BL - 1) / BL;
   const bool slow = d.tile_dups || d.tile_maxk > kTileFastK;
-  for (int k = tid; k <= ntl; k += TH) Lb[k] = d.lm_begin[l0 + k];
-  for (int k = tid; k < ntl; k += TH) Lu[k] = d.lm_urange[l0 + k];
-  for (int li = tid; li < ntl; li += TH) damp_factor(d.lm_R + 8 * (l0 + li), d.lm_b + 4 * (l0 + li), lambda, Lr[li], Lw[li]);
-  for (int k = tid; k < 3 * ntl; k += TH) {
-    const int li = k / 3, c = k - 3 * li;
-    Lx[li][c] = d.X[0][4 * (l0 + li) + c];
-  }
-  {
-    const int cb = d.tile_cam_ptr[t];
-    for (int k = tid; k < 16 * cp; k += TH) {
-      const int u = k >> 4, c = k & 15;
-      Lc[u][c] = d.pose_rt[0][16 * d.hidx_pose[d.tile_cams[cb + u]] + c];
-    }
-    if (ST)
-      for (int u = tid; u < cp; u += TH) Lbf[u] = d.pose_bf[d.hidx_pose[d.tile_cams[cb + u]]];
-  }
-  for (int bt = tid; bt < nbatch; bt += TH) {  // batch spans from the landmarks' camera ranges
-    int cmin = 1 << 30, cmax = -1;
-    for (int li = BL * bt; li < min(BL * bt + BL, ntl); ++li) {
-      const int2 ur = d.lm_urange[l0 + li];
-      if (ur.x >= 0) { cmin = min(cmin, 6 * ur.x); cmax = max(cmax, 6 * ur.y + 6); }
-    }
-    Bs[bt] = int2{cmin, cmax};
-  }
+  tile_preamble<ST>(d, t, cp, l0, ntl, nbatch, lambda, tid, Ys, Lb, Lw, Lr, Lx, Lc, Lbf, Bs);
   __syncthreads();
   // prefetched raw inputs of one batch (fast path): thread tid owns observation b0 + tid
   double ps = 0.0, pur = -1.0;
@@ -1203,48 +1303,19 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
     if (!slow) {
       if (pu >= 0) {  // Y block of the observation: (R'^-1)^T jl^T jp, Jacobians recomputed once
         const double *pr = Lc[pu], *xl = Lx[pli], *r = Lr[pli];
-        MonoEval m;
-        m.x = pr[0] * xl[0] + pr[1] * xl[1] + pr[2] * xl[2] + pr[9];
-        m.y = pr[3] * xl[0] + pr[4] * xl[1] + pr[5] * xl[2] + pr[10];
-        m.z = pr[6] * xl[0] + pr[7] * xl[1] + pr[8] * xl[2] + pr[11];
-        m.s = ps;
         const int row = 3 * (pli - lb), col = 6 * pu;
+        // the stereo branch's camera-frame point, ahead of the branch (there it
+        // costs the stereo kernels registers: NT = 4 a wave per SIMD); a mono
+        // observation's Y needs no more than stage_mono_y's own
+        MonoEval m;
+        if (ST) {
+          m.x = pr[0] * xl[0] + pr[1] * xl[1] + pr[2] * xl[2] + pr[9];
+          m.y = pr[3] * xl[0] + pr[4] * xl[1] + pr[5] * xl[2] + pr[10];
+          m.z = pr[6] * xl[0] + pr[7] * xl[1] + pr[8] * xl[2] + pr[11];
+          m.s = ps;
+        }
         if (!(ST && pur >= 0.0)) {
-          // mono: jl = s J_pi R and jp = s J_pi [-[X_c]x | I] (types_six_dof_expmap.cpp:
-          // 103-139), so P = jl^T jp = [-B' [X_c]x | B'] with B' = R^T A,
-          // A = s^2 J_pi^T J_pi (3x3, five distinct entries), and Y = R'^-T P =
-          // [-B [X_c]x | B], B = R'^-T R^T A: ~45 % fewer FP64 operations than
-          // forming jl, jp and their 18 products
-          const double iz = 1.0 / m.z, xz = m.x * iz, yz = m.y * iz, fx = pr[12], fy = pr[13];
-          const double t00 = -iz * fx, t02 = (xz * iz) * fx, t11 = -iz * fy, t12 = (yz * iz) * fy;
-          const double s2 = ps * ps;
-          const double A00 = s2 * (t00 * t00), A02 = s2 * (t00 * t02), A11 = s2 * (t11 * t11),
-                       A12 = s2 * (t11 * t12), A22 = s2 * (t02 * t02 + t12 * t12);
-          double Q[3][3];  // R^T A
-#pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            Q[i][0] = pr[i] * A00 + pr[6 + i] * A02;
-            Q[i][1] = pr[3 + i] * A11 + pr[6 + i] * A12;
-            Q[i][2] = pr[i] * A02 + pr[3 + i] * A12 + pr[6 + i] * A22;
-          }
-#pragma unroll
-          for (int j = 0; j < 3; ++j) {  // B = R'^-T Q (R'^-1 upper: r0 r1 r2 / r3 r4 / r5)
-            const double b0 = r[0] * Q[0][j], b1 = r[1] * Q[0][j] + r[3] * Q[1][j],
-                         b2 = r[2] * Q[0][j] + r[4] * Q[1][j] + r[5] * Q[2][j];
-            Q[0][j] = b0;
-            Q[1][j] = b1;
-            Q[2][j] = b2;
-          }
-#pragma unroll
-          for (int q = 0; q < 3; ++q) {
-            double *yr = &Y[row + q][col];
-            yr[0] = Q[q][2] * m.y - Q[q][1] * m.z;
-            yr[1] = Q[q][0] * m.z - Q[q][2] * m.x;
-            yr[2] = Q[q][1] * m.x - Q[q][0] * m.y;
-            yr[3] = Q[q][0];
-            yr[4] = Q[q][1];
-            yr[5] = Q[q][2];
-          }
+          stage_mono_y(pr, xl, r, ps, &Y[row][0], NC, col);
         } else {  // stereo: the third row's Jacobians join the products
           double jl[6], jp[12], jl3[3], jp3[6];
           mono_jac(pr, m, jl, jp);
@@ -1297,9 +1368,7 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
       TP(4);
       if (gcol >= cmin && gcol < cmax) {
         double gs = 0.0;
-        for (int li = 0; li < nl; ++li)
-          gs += Y[3 * li][gcol] * Lw[lb + li][0] + Y[3 * li + 1][gcol] * Lw[lb + li][1] +
-                Y[3 * li + 2][gcol] * Lw[lb + li][2];
+        for (int li = 0; li < nl; ++li) gs += tile_grad_term(Y, Lw[lb + li], li, gcol);
         gacc -= gs;
       }
       prev = int2{cmin, cmax};
@@ -1311,42 +1380,8 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
     TP(6);
   }
   TP_STORE;
-  if (d.cr_direct) {  // this tile's share of clearing the CR superblocks that k_rcs_reduce fills next
-    const int64_t tot = (int64_t)d.cr_p * d.cr_n * d.cr_n;  // doubles per array (even: n % 16 == 0)
-    const int64_t per = ((tot + d.n_tiles - 1) / d.n_tiles + 1) & ~(int64_t)1;
-    const int64_t a0 = (int64_t)t * per, a1 = min(tot, a0 + per);
-    for (int64_t k = a0 + 2 * tid; k < a1; k += 2 * TH) {
-      store2(d.cr_D + k, 0.0, 0.0);
-      store2(d.cr_E + k, 0.0, 0.0);
-    }
-  }
-  // write -G_t as the tile's partial, block-major (tile_blk): element (R, C) of
-  // an upper 16x16 tile goes to block (R/6, C/6) if that block is upper; a
-  // diagonal block straddling two tiles also gets the mirror of the elements
-  // whose transpose falls in the (never computed) lower tile
-  double *out = d.part + d.tile_part_ptr[t];
-  const int n6 = 6 * cp;
-  int q = 0;
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-    for (int tj = ti; tj < NT; ++tj, ++q) {
-      if (q % kTileWaves == wave && tj < nt) {
-        const int C = tj * 16 + r16, w = C / 6, c = C - 6 * w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int R = ti * 16 + k4 + 4 * j, u = R / 6, r = R - 6 * u;
-          if (R < n6 && C < n6 && u <= w) {
-            double *blk = out + 36 * tile_blk(u, w, cp);
-            const double v = -acc[q / kTileWaves][j];
-            blk[6 * r + c] = v;
-            if (u == w && ti < tj) blk[6 * c + r] = v;
-          }
-        }
-      }
-    }
-  double *go = d.gpart + d.tile_gpart_ptr[t];
-  if (gcol >= 0 && gcol < ncol) go[gcol] = gacc;
+  tile_cr_clear(d, t, tid);
+  tile_write_partial<NT, kTileWaves>(d, t, cp, wave, acc, gacc, tid);
 }
 
 // ---- producer / consumer RCS tiles (mono, no repeated cameras) ----
@@ -1359,63 +1394,19 @@ __global__ __launch_bounds__(kTileThreads, ST ? 2 : tile_occ<NT>()) void k_rcs_t
 // one LDS buffer, wave 0 clears the entries it staged two batches ago in the
 // other buffer and stages batch b + 1 there (two observations per lane, so a
 // batch of up to 128 observations is one pass, and the two chains give the
-// lone wave some ILP); ONE barrier per batch hands the buffers over. Every
-// accumulator tile sums the same products in the same order as k_rcs_tile
-// (only its owner wave changes) and the gradient code is the same: the
-// partials are bitwise identical to k_rcs_tile's.
+// lone wave some ILP); ONE barrier per batch hands the buffers over. The
+// preamble, the staging of a mono observation (stage_mono_y), the MFMA pair
+// loop, the gradient terms and the write-out are the shared functions above,
+// instantiated with kTileCons owner waves instead of kTileWaves: every
+// accumulator tile sums the same products in the same order (only its owner
+// wave changes), so the partials are bitwise identical to k_rcs_tile's.
 constexpr int kTileCons = kTileWaves - 1;  // consumer waves
-// Wide classes (NT >= 8) one K step at a time (its NT operand tiles in
-// registers, then every owned pair of the span): each accumulator still adds
-// its K steps in order, so the sums are the same bits as k_rcs_tile's, with a
-// third of the operand registers (NT = 8: 155 -> 124 VGPRs, 4 waves per SIMD;
-// NT = 9 fits 3). The narrow classes keep all operands loaded at once (the
-// stepped form of NT = 4 spilled).
+// The wide classes (NT >= 8) run tile_mfma's K-stepped form (NT = 8: 155 ->
+// 124 VGPRs, 4 waves per SIMD; NT = 9 fits 3). The narrow classes keep all
+// operands loaded at once (the stepped form of NT = 4 spilled).
 #ifndef SQLM_TILE_KS_STEP_MIN
 #define SQLM_TILE_KS_STEP_MIN 8
 #endif
-template <int NT, int P, int NC>
-__device__ __forceinline__ void tile_mfma_cons(d4v *acc, const double (*Y)[NC], int tmin, int tmax, int nks, int r16,
-                                               int k4) {
-  if constexpr (NT >= SQLM_TILE_KS_STEP_MIN) {
-#pragma unroll
-  for (int ks = 0; ks < kTileKS; ++ks) {
-    if (ks < nks) {
-      double op[NT];
-#pragma unroll
-      for (int t = 0; t < NT; ++t) op[t] = Y[4 * ks + k4][t * 16 + r16];
-      int q = 0;
-#pragma unroll
-      for (int ti = 0; ti < NT; ++ti) {
-#pragma unroll
-        for (int tj = ti; tj < NT; ++tj, ++q) {
-          if (q % kTileCons == P && ti >= tmin && tj <= tmax)
-            acc[q / kTileCons] = __builtin_amdgcn_mfma_f64_16x16x4f64(op[ti], op[tj], acc[q / kTileCons], 0, 0, 0);
-        }
-      }
-    }
-  }
-  } else {
-    double op[NT][kTileKS];
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int ks = 0; ks < kTileKS; ++ks) op[t][ks] = Y[4 * ks + k4][t * 16 + r16];
-    int q = 0;
-#pragma unroll
-    for (int ti = 0; ti < NT; ++ti) {
-#pragma unroll
-      for (int tj = ti; tj < NT; ++tj, ++q) {
-        if (q % kTileCons == P && ti >= tmin && tj <= tmax) {
-#pragma unroll
-          for (int ks = 0; ks < kTileKS; ++ks)
-            if (ks < nks)
-              acc[q / kTileCons] =
-                  __builtin_amdgcn_mfma_f64_16x16x4f64(op[ti][ks], op[tj][ks], acc[q / kTileCons], 0, 0, 0);
-        }
-      }
-    }
-  }
-}
 
 // observations a producer lane stages per batch (lane, lane + 64): batches of
 // up to kProdObs observations take the producer path
@@ -1431,7 +1422,6 @@ __device__ __forceinline__ void tile_consumer(const DevProblem &d, int t, int cp
                                               const int2 *Bs, int tid) {
   constexpr int NQ = NT * (NT + 1) / 2, NQW = (NQ + kTileCons - 1) / kTileCons, BL = kTileBL;
   const int lane = tid & 63, r16 = lane & 15, k4 = lane >> 4, gcol = tid - 64;
-  const int ncol = 6 * cp, nt = (ncol + 15) >> 4;
   d4v acc[NQW];
 #pragma unroll
   for (int q = 0; q < NQW; ++q) acc[q] = d4v{0.0, 0.0, 0.0, 0.0};
@@ -1446,12 +1436,10 @@ __device__ __forceinline__ void tile_consumer(const DevProblem &d, int t, int cp
     const int cmin = __builtin_amdgcn_readfirstlane(bsp.x), cmax = __builtin_amdgcn_readfirstlane(bsp.y);
     if (cmax > 0) {
       const int tmin = cmin >> 4, tmax = (cmax - 1) >> 4;
-      tile_mfma_cons<NT, P>(acc, Y, tmin, tmax, (3 * nl + 3) >> 2, r16, k4);
+      tile_mfma<NT, kTileCons, P, (NT >= SQLM_TILE_KS_STEP_MIN)>(acc, Y, tmin, tmax, (3 * nl + 3) >> 2, r16, k4);
       if (gcol >= cmin && gcol < cmax) {
         double gs = 0.0;
-        for (int li = 0; li < nl; ++li)
-          gs += Y[3 * li][gcol] * Lw[lb + li][0] + Y[3 * li + 1][gcol] * Lw[lb + li][1] +
-                Y[3 * li + 2][gcol] * Lw[lb + li][2];
+        for (int li = 0; li < nl; ++li) gs += tile_grad_term(Y, Lw[lb + li], li, gcol);
         gacc -= gs;
       }
     }
@@ -1460,30 +1448,7 @@ __device__ __forceinline__ void tile_consumer(const DevProblem &d, int t, int cp
     TP(3);  // consumer: waiting for the producer
   }
   if (P == 0) TP_STORE_BY(64);
-  // -G_t as the tile's partial, block-major (as k_rcs_tile)
-  double *out = d.part + d.tile_part_ptr[t];
-  const int n6 = 6 * cp;
-  int q = 0;
-#pragma unroll
-  for (int ti = 0; ti < NT; ++ti)
-#pragma unroll
-    for (int tj = ti; tj < NT; ++tj, ++q) {
-      if (q % kTileCons == P && tj < nt) {
-        const int C = tj * 16 + r16, w = C / 6, c = C - 6 * w;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int R = ti * 16 + k4 + 4 * j, u = R / 6, r = R - 6 * u;
-          if (R < n6 && C < n6 && u <= w) {
-            double *blk = out + 36 * tile_blk(u, w, cp);
-            const double v = -acc[q / kTileCons][j];
-            blk[6 * r + c] = v;
-            if (u == w && ti < tj) blk[6 * c + r] = v;
-          }
-        }
-      }
-    }
-  double *go = d.gpart + d.tile_gpart_ptr[t];
-  if (gcol >= 0 && gcol < ncol) go[gcol] = gacc;
+  tile_write_partial<NT, kTileCons>(d, t, cp, P, acc, gacc, tid);
 }
 
 // waves per SIMD k_rcs_tile_p is compiled for: the consumer waves' registers
@@ -1497,7 +1462,7 @@ constexpr int tile_p_occ() {
 }
 template <int NT>
 __global__ __launch_bounds__(kTileThreads, tile_p_occ<NT>()) void k_rcs_tile_p(DevProblem d, double lambda, int cls_off) {
-  constexpr int TH = kTileThreads, NC = NT * 16, BL = kTileBL;
+  constexpr int NC = NT * 16, BL = kTileBL;
   __shared__ double Ys[2][kTileRows][NC];
   __shared__ int Lb[kTileMaxLm + 1];
   __shared__ double Lw[kTileMaxLm][3];
@@ -1510,39 +1475,10 @@ __global__ __launch_bounds__(kTileThreads, tile_p_occ<NT>()) void k_rcs_tile_p(D
   const int cp = d.tile_cam_ptr[t + 1] - d.tile_cam_ptr[t];
   static_assert(NT * 16 <= kTileThreads - 64, "one gradient column per thread of waves 1..");
   static_assert(kTileHardCams <= 32, "the producer's staged-position code holds a camera in 5 bits");
-  for (int k = tid; k < 2 * kTileRows * NC; k += TH) (&Ys[0][0][0])[k] = 0.0;
   const int l0 = d.tile_lm_ptr[t], l1 = d.tile_lm_ptr[t + 1], ntl = l1 - l0;
   const int nbatch = (ntl + BL - 1) / BL;
-  for (int k = tid; k <= ntl; k += TH) Lb[k] = d.lm_begin[l0 + k];
-  for (int li = tid; li < ntl; li += TH) damp_factor(d.lm_R + 8 * (l0 + li), d.lm_b + 4 * (l0 + li), lambda, Lr[li], Lw[li]);
-  for (int k = tid; k < 3 * ntl; k += TH) {
-    const int li = k / 3, c = k - 3 * li;
-    Lx[li][c] = d.X[0][4 * (l0 + li) + c];
-  }
-  {
-    const int cb = d.tile_cam_ptr[t];
-    for (int k = tid; k < 16 * cp; k += TH) {
-      const int u = k >> 4, c = k & 15;
-      Lc[u][c] = d.pose_rt[0][16 * d.hidx_pose[d.tile_cams[cb + u]] + c];
-    }
-  }
-  for (int bt = tid; bt < nbatch; bt += TH) {  // batch spans from the landmarks' camera ranges
-    int cmin = 1 << 30, cmax = -1;
-    for (int li = BL * bt; li < min(BL * bt + BL, ntl); ++li) {
-      const int2 ur = d.lm_urange[l0 + li];
-      if (ur.x >= 0) { cmin = min(cmin, 6 * ur.x); cmax = max(cmax, 6 * ur.y + 6); }
-    }
-    Bs[bt] = int2{cmin, cmax};
-  }
-  if (d.cr_direct) {  // this tile's share of clearing the CR superblocks that k_rcs_reduce fills next
-    const int64_t tot = (int64_t)d.cr_p * d.cr_n * d.cr_n;
-    const int64_t per = ((tot + d.n_tiles - 1) / d.n_tiles + 1) & ~(int64_t)1;
-    const int64_t a0 = (int64_t)t * per, a1 = min(tot, a0 + per);
-    for (int64_t k = a0 + 2 * tid; k < a1; k += 2 * TH) {
-      store2(d.cr_D + k, 0.0, 0.0);
-      store2(d.cr_E + k, 0.0, 0.0);
-    }
-  }
+  tile_preamble<false>(d, t, cp, l0, ntl, nbatch, lambda, tid, Ys, Lb, Lw, Lr, Lx, Lc, nullptr, Bs);
+  tile_cr_clear(d, t, tid);
   __syncthreads();
   // Two role loops with the same number of barriers (nbatch + 1): between
   // barriers b - 1 and b the producer stages batch b into buffer b & 1 while
@@ -1836,28 +1772,31 @@ __global__ __launch_bounds__(kRedThreads) void k_rcs_reduce(DevProblem d, double
 #ifndef SQLM_TILE_PROD_MAXNT
 #define SQLM_TILE_PROD_MAXNT 9
 #endif
-template <int NTT>
-void launch_tile_p(int cnt, hipStream_t S, const DevProblem &d, double lambda, int off) {
-  if constexpr (NTT <= SQLM_TILE_PROD_MAXNT)
-    hipLaunchKernelGGL((k_rcs_tile_p<NTT>), dim3(cnt), dim3(kTileThreads), 0, S, d, lambda, off);
-  else
-    hipLaunchKernelGGL((k_rcs_tile<NTT, false>), dim3(cnt), dim3(kTileThreads), 0, S, d, lambda, off);
-}
-
 int rcs_tile_kernel(const DevProblem &d) {
-  if (d.nP == 0 || d.n_tiles <= 0) return 0;
-  if (d.has_stereo) return 3;
+  if (d.nP == 0 || d.n_tiles <= 0) return kTileKernelNone;
+  if (d.has_stereo) return kTileKernelStereo;
   // mono tiles without repeated cameras whose batches fit the producer wave:
   // the producer / consumer kernel
   const bool prod_tiles = !d.tile_dups && d.tile_maxk * kTileBL <= kProdObs && d.tile_prod;
-  return prod_tiles ? 4 : 2;
+  return prod_tiles ? kTileKernelProducer : kTileKernelMono;
 }
 
-void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k, hipStream_t st,
-                      const TileStreams *ts) {
+// the tiles of accumulator-width class NT on stream S, with the kernel `kern` (rcs_tile_kernel) names
+template <int NT>
+static void launch_tile_class(const DevProblem &d, double lambda, int kern, hipStream_t S) {
+  const int cnt = d.tile_cls_cnt[NT], off = d.tile_cls_off[NT];
+  if (cnt <= 0) return;
+  const dim3 grid(cnt), block(kTileThreads);
+  if (kern == kTileKernelStereo)
+    hipLaunchKernelGGL((k_rcs_tile<NT, true>), grid, block, 0, S, d, lambda, off);
+  else if (kern == kTileKernelProducer && NT <= SQLM_TILE_PROD_MAXNT)
+    hipLaunchKernelGGL((k_rcs_tile_p<NT>), grid, block, 0, S, d, lambda, off);
+  else
+    hipLaunchKernelGGL((k_rcs_tile<NT, false>), grid, block, 0, S, d, lambda, off);
+}
+
+void launch_rcs_tiles(const DevProblem &d, double lambda, hipStream_t st, const TileStreams *ts) {
   if (d.nP == 0) return;
-  (void)max_k;
-  (void)max_cp;
   if (d.n_tiles > 0) {
     // one launch per accumulator-width class (4, 6, 8, 9); the classes go to
     // three streams so that no launch's tail leaves the chip idle: 8 (the
@@ -1887,24 +1826,12 @@ void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k,
       (void)hipEventRecord(ts->fork, st);
       TH_MARK;
     }
-    const bool prod_tiles = rcs_tile_kernel(d) == 4;
-#define SQLM_TILE(NTT, S)                                                                                     \
-  do {                                                                                                        \
-    const int cnt = d.tile_cls_cnt[NTT], off = d.tile_cls_off[NTT];                                            \
-    if (cnt > 0) {                                                                                            \
-      if (d.has_stereo)                                                                                       \
-        hipLaunchKernelGGL((k_rcs_tile<NTT, true>), dim3(cnt), dim3(kTileThreads), 0, S, d, lambda, off);      \
-      else if (prod_tiles)                                                                                    \
-        launch_tile_p<NTT>(cnt, S, d, lambda, off);                                                           \
-      else                                                                                                    \
-        hipLaunchKernelGGL((k_rcs_tile<NTT, false>), dim3(cnt), dim3(kTileThreads), 0, S, d, lambda, off);     \
-    }                                                                                                         \
-  } while (0)
+    const int kern = rcs_tile_kernel(d);
     // (the chain 9, 4, 3 on the context stream instead, so that the reduce
     // follows its last kernel in-queue: within noise, profiles/r05/
     // ab_stream_order_rejected.log)
     const hipStream_t sm = par ? ts->s[0] : st, sn = par ? ts->s[1] : st;
-    SQLM_TILE(8, st);
+    launch_tile_class<8>(d, lambda, kern, st);
     // the side streams' waits (≈10 us of host time each) after the first
     // class is on its way: the fork event already marks st's position before it
     // (tile phase 0.520 -> 0.516 ms, profiles/r05/ab_tile_first8_r5p.log)
@@ -1915,11 +1842,12 @@ void launch_rcs_tiles(const DevProblem &d, double lambda, int max_cp, int max_k,
     TH_MARK;
     // (4 behind 6, or behind 8: config 4 777 -> 776 / 761 it/s,
     // profiles/r05/ab_tile_stream_assign_rejected.log)
-    SQLM_TILE(6, sm);
+    launch_tile_class<6>(d, lambda, kern, sm);
     TH_MARK;
-    SQLM_TILE(9, sn); SQLM_TILE(4, sn); SQLM_TILE(3, sn);
+    launch_tile_class<9>(d, lambda, kern, sn);
+    launch_tile_class<4>(d, lambda, kern, sn);
+    launch_tile_class<3>(d, lambda, kern, sn);
     TH_MARK;
-#undef SQLM_TILE
     if (par) {
       (void)hipEventRecord(ts->join[0], ts->s[0]);
       (void)hipEventRecord(ts->join[1], ts->s[1]);

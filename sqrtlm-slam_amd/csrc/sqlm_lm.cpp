@@ -264,7 +264,7 @@ int trial_launch(sqlm_ctx *c, double lambda, bool &cam_after) {
   launch_damp(d, lambda, c->stream);
   tmark(c, 2, true);
   tmark(c, 3, false);
-  if (c->use_tiles) launch_rcs_tiles(d, lambda, c->tile_max_cp, c->tile_max_k, c->stream, &c->tiles);
+  if (c->use_tiles) launch_rcs_tiles(d, lambda, c->stream, &c->tiles);
   else launch_rcs(d, lambda, c->plan.max_row_blocks, c->stream);
   tmark(c, 3, true);
   hmark(c, 1);  // damp + tile launches

@@ -512,8 +512,6 @@ int plan_tiles_and_solver(sqlm_ctx *c, const ObsArrays &oa, int *obs_loc, PhaseT
   phase("tile lists");
   if (phase.on) print_plan(pl, tp);
   c->use_tiles = nP > 0 && tp.max_cp <= kTileHardCams;
-  c->tile_max_cp = tp.max_cp;
-  c->tile_max_k = 0;
   if (!c->use_tiles && pl.max_row_blocks > 128) return SQLM_ERR_UNSUPPORTED;
   return SQLM_OK;
 }

@@ -59,6 +59,12 @@ CASES = {
     "rows": (lambda: _track(40, 500, 26, 30, 22), 1.0, {}),
     "stereo_half": (lambda: _stereo(0.5), 1.0, {}),
     "stereo_all": (lambda: _stereo(1.0), 1.0, {}),
+    # the widest stereo tiles (stereo_half / stereo_all reach classes 3, 4 and 6 only):
+    # the geometry of cls8 / cls9, every second observation stereo
+    "stereo_cls8": (lambda: synth.add_stereo(_track(36, 900, 18, 19, 18), 0.5, seed=18, robust_delta=HUBER_STEREO),
+                    1.0, {}),
+    "stereo_cls9": (lambda: synth.add_stereo(_track(40, 900, 22, 23, 19), 0.5, seed=19, robust_delta=HUBER_STEREO),
+                    1.0, {}),
     "dups": (_dups, 1.0, {}),
     # 5 free cameras, 125 tiles: every S block / g row sums > 24 partials
     "long_red": (lambda: _track(6, 2000, 6, 6, 24), 1.0, {}),

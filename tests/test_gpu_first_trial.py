@@ -74,6 +74,8 @@ EXPECT = {
     "rows": ("rows", set(), "dense"),
     "stereo_half": ("tile_stereo", None, None),
     "stereo_all": ("tile_stereo", None, None),
+    "stereo_cls8": ("tile_stereo", {8}, None),
+    "stereo_cls9": ("tile_stereo", {9}, None),
     "dups": ("tile_mono", None, None),
     "long_red": ("tile_producer", {3}, None),
     "cr_levels": ("tile_producer", None, "band"),
