@@ -224,6 +224,68 @@ int sqlm_sim3_get_pair_chi2(sqlm_ctx *ctx, double *chi2);
 int sqlm_sim3_get_linearization(sqlm_ctx *ctx, double *e, double *J);
 int sqlm_sim3_get_last_step(sqlm_ctx *ctx, int prob, double *H, double *b, double *dx);
 
+/* Sim3 RANSAC of loop candidates: Sim3Solver (src/algorithm/Sim3Solver.cc),
+ * every hypothesis of n_prob candidates in one launch. A problem follows the
+ * conventions of sqlm_sim3_optimize: its pairs are the correspondences the
+ * constructor keeps (:78-127), X1c / X2c are the two map points in their own
+ * cameras (float values carried in doubles, rounded to float on entry), the
+ * targets mvP1im1 / mvP2im2 are the library's own projections of those points
+ * (FromCameraToImage, :543-562). max_err1 / max_err2 are mvnMaxError1/2 as
+ * stored: the reference keeps 9.210 * sigma2 in a std::vector<size_t>, so the
+ * caller truncates to an integer and the test err < maxErr compares a float
+ * with that integer converted to float.
+ * Hypothesis h of a problem with N pairs uses draws[h][0..2], the raw
+ * DUtils::Random::RandomInt(0, size-1) values of :243, draws[h][i] in
+ * [0, N-1-i]; the library maps them to pair indices as the swap-remove of
+ * :236-256 does. Per hypothesis: ComputeSim3 (:319-458) and CheckInliers
+ * (:462-490) in float, one rule for what the source leaves to OpenCV (products
+ * and sums in double, one rounding per stored element), and the eigenvector of
+ * step 4 by a fixed-sweep cyclic Jacobi iteration in double instead of
+ * cv::eigen + cv::Rodrigues. A NaN or Inf transform has 0
+ * inliers. Then, per problem, the sequential bookkeeping of iterate()
+ * (:264-284) over the counts c_h with a running best b (initially 0):
+ * flags[h] bit 0 = hypothesis h updates the best (c_h >= b), bit 1 = it also
+ * returns (c_h > min_inliers); b carries on across returns. first_return is
+ * the first returning hypothesis of the problem or -1, best the last one that
+ * updated the best (-1 without hypotheses); both count from the problem's
+ * first hypothesis. A problem with hypotheses and fewer than 3 pairs, a
+ * negative threshold or a draw out of range is SQLM_ERR_INVALID_ARG. */
+int sqlm_sim3_ransac(sqlm_ctx *ctx, int n_prob,
+    const double *intr1, const double *intr2,   /* [n_prob][4] fx fy cx cy of KF1 / KF2              */
+    const uint8_t *fix_scale,     /* [n_prob]                                                          */
+    const int32_t *min_inliers,   /* [n_prob] mRansacMinInliers                                        */
+    const int64_t *pair_off,      /* [n_prob+1] CSR offsets into the pair arrays                       */
+    const double *X1c, const double *X2c,       /* [n_pair][3]                                        */
+    const int32_t *max_err1, const int32_t *max_err2, /* [n_pair], >= 0                                */
+    const int64_t *hyp_off,       /* [n_prob+1] CSR offsets into the per-hypothesis arrays             */
+    const int32_t *draws,         /* [n_hyp][3]                                                        */
+    int32_t *n_inliers,           /* [n_hyp] mnInliersi                                                */
+    uint8_t *flags,               /* [n_hyp]                                                           */
+    float *R12, float *t12, float *s12,         /* [n_hyp][9] row-major, [n_hyp][3], [n_hyp]          */
+    int32_t *first_return, int32_t *best);      /* [n_prob]                                           */
+/* Of the last sqlm_sim3_ransac of the context (SQLM_ERR_STATE before any):
+ * mvbInliersi of hypothesis `hyp` of problem `prob`, mask [N] of 0 / 1; and the
+ * three pair indices it drew with the float T12 and T21 (4x4 row-major) that
+ * CheckInliers used (any of idx, T12, T21 may be NULL, not all). */
+int sqlm_sim3_ransac_get_inliers(sqlm_ctx *ctx, int prob, int hyp, uint8_t *mask);
+int sqlm_sim3_ransac_get_hypothesis(sqlm_ctx *ctx, int prob, int hyp, int32_t idx[3], float T12[16], float T21[16]);
+/* Host only, no context. mRansacMaxIts after SetRansacParameters(probability,
+ * min_inliers, max_iterations) on n_pair correspondences (:145-203), the
+ * number of hypotheses of a problem: max(1, min(ceil(log(1-p) / log(1 -
+ * pow((float)min_inliers / n_pair, 3))), max_iterations)), clamped in double
+ * before the conversion to int; 1 if min_inliers == n_pair; 0 if n_pair <
+ * min_inliers, where iterate() gives up at once (:214-218). */
+int sqlm_sim3_ransac_max_its(int64_t n_pair, double probability, int min_inliers, int max_iterations);
+/* Host only: the bookkeeping above on given counts; first_return / best may be NULL. */
+int sqlm_sim3_ransac_scan(int64_t n_hyp, const int32_t *counts, int min_inliers, uint8_t *flags,
+    int64_t *first_return, int64_t *best);
+/* Host only: one hypothesis of one problem evaluated on the CPU by the source
+ * text the kernel is compiled from (diagnostics and CPU tests). */
+int sqlm_sim3_ransac_hypothesis_host(int n_pair, const double intr1[4], const double intr2[4], int fix_scale,
+    const double *X1c, const double *X2c, const int32_t *max_err1, const int32_t *max_err2, const int32_t draws[3],
+    int32_t idx[3], float R12[9], float t12[3], float *s12, float T12[16], float T21[16], uint8_t *mask,
+    int32_t *n_inliers);
+
 /* Motion-only bundle adjustment: g2oOptimizer::PoseOptimization
  * (g2oOptimizer.cc:385-679), n_prob independent problems in one call (Tracking's
  * call is n_prob = 1, Relocalization's candidates are a batch). One free

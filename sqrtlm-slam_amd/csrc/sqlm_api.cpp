@@ -145,6 +145,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   comm_destroy(c->comm);
   if (c->eg) eg_destroy(c->eg);
   if (c->sim3) sim3_destroy(c->sim3);
+  if (c->ransac) ransac_destroy(c->ransac);
   if (c->pose) pose_destroy(c->pose);
   if (c->lidar) lidar_destroy(c->lidar);
   if (c->orb) orb_destroy(c->orb);
@@ -421,6 +422,70 @@ int sqlm_sim3_get_last_step(sqlm_ctx *c, int prob, double *H, double *b, double 
   if (!c || !H || !b || !dx) return SQLM_ERR_INVALID_ARG;
   if (!c->sim3) return SQLM_ERR_STATE;
   return sim3_get_last_step(c->sim3, prob, H, b, dx);
+}
+
+int sqlm_sim3_ransac(sqlm_ctx *c, int n_prob, const double *intr1, const double *intr2, const uint8_t *fix_scale,
+                     const int32_t *min_inliers, const int64_t *pair_off, const double *X1c, const double *X2c,
+                     const int32_t *max_err1, const int32_t *max_err2, const int64_t *hyp_off, const int32_t *draws,
+                     int32_t *n_inliers, uint8_t *flags, float *R12, float *t12, float *s12, int32_t *first_return,
+                     int32_t *best) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  RansacArgs a;
+  a.n_prob = n_prob;
+  a.intr1 = intr1; a.intr2 = intr2; a.fix_scale = fix_scale; a.min_inliers = min_inliers; a.pair_off = pair_off;
+  a.X1c = X1c; a.X2c = X2c; a.max_err1 = max_err1; a.max_err2 = max_err2; a.hyp_off = hyp_off; a.draws = draws;
+  a.n_inliers = n_inliers; a.flags = flags; a.R12 = R12; a.t12 = t12; a.s12 = s12;
+  a.first_return = first_return; a.best = best;
+  if (int r = ransac_args_ok(a)) return r;
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  if (!c->ransac && !(c->ransac = ransac_create(c->stream))) return SQLM_ERR_OOM;
+  return ransac_run(c->ransac, a);
+}
+
+int sqlm_sim3_ransac_get_inliers(sqlm_ctx *c, int prob, int hyp, uint8_t *mask) {
+  if (!c || !mask) return SQLM_ERR_INVALID_ARG;
+  if (!c->ransac) return SQLM_ERR_STATE;
+  return ransac_get_inliers(c->ransac, prob, hyp, mask);
+}
+
+int sqlm_sim3_ransac_get_hypothesis(sqlm_ctx *c, int prob, int hyp, int32_t idx[3], float T12[16], float T21[16]) {
+  if (!c || (!idx && !T12 && !T21)) return SQLM_ERR_INVALID_ARG;
+  if (!c->ransac) return SQLM_ERR_STATE;
+  return ransac_get_hypothesis(c->ransac, prob, hyp, idx, T12, T21);
+}
+
+int sqlm_sim3_ransac_max_its(int64_t n_pair, double probability, int min_inliers, int max_iterations) {
+  return ransac_max_its(n_pair, probability, min_inliers, max_iterations);
+}
+
+int sqlm_sim3_ransac_scan(int64_t n_hyp, const int32_t *counts, int min_inliers, uint8_t *flags,
+                          int64_t *first_return, int64_t *best) {
+  if (n_hyp < 0 || (n_hyp > 0 && (!counts || !flags))) return SQLM_ERR_INVALID_ARG;
+  ransac_scan(n_hyp, counts, min_inliers, flags, first_return, best);
+  return SQLM_OK;
+}
+
+int sqlm_sim3_ransac_hypothesis_host(int n_pair, const double intr1[4], const double intr2[4], int fix_scale,
+                                     const double *X1c, const double *X2c, const int32_t *max_err1,
+                                     const int32_t *max_err2, const int32_t draws[3], int32_t idx[3], float R12[9],
+                                     float t12[3], float *s12, float T12[16], float T21[16], uint8_t *mask,
+                                     int32_t *n_inliers) {
+  if (!intr1 || !intr2 || !X1c || !X2c || !max_err1 || !max_err2 || !draws || !idx || !R12 || !t12 || !s12 || !T12 ||
+      !T21 || !mask || !n_inliers)
+    return SQLM_ERR_INVALID_ARG;
+  float h[34];  // RansacHyp: R 9, t 3, s, sR 9, sRinv 9, tinv 3
+  if (int r = ransac_hypothesis_host(n_pair, intr1, intr2, fix_scale, X1c, X2c, max_err1, max_err2, draws, idx, h,
+                                     mask, n_inliers))
+    return r;
+  std::memcpy(R12, h, 9 * sizeof(float));
+  std::memcpy(t12, h + 9, 3 * sizeof(float));
+  *s12 = h[12];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      T12[4 * i + j] = i == 3 ? (j == 3 ? 1.f : 0.f) : (j == 3 ? h[9 + i] : h[13 + 3 * i + j]);
+      T21[4 * i + j] = i == 3 ? (j == 3 ? 1.f : 0.f) : (j == 3 ? h[31 + i] : h[22 + 3 * i + j]);
+    }
+  return SQLM_OK;
 }
 
 namespace {

@@ -94,6 +94,7 @@ struct sqlm_ctx {
   bool need_maxdiag = false;
   sqlm::EGSolver *eg = nullptr;
   sqlm::Sim3Solver *sim3 = nullptr;
+  sqlm::RansacSolver *ransac = nullptr;  // sqlm_sim3_ransac (sqlm_sim3_ransac.cpp)
   sqlm::PoseSolver *pose = nullptr;
   sqlm::LidarSolver *lidar = nullptr;
   sqlm::OrbEngine *orb = nullptr;

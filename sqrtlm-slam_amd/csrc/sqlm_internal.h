@@ -483,6 +483,59 @@ int sim3_get_pair_chi2(const Sim3Solver *s, double *chi2);
 int sim3_get_linearization(const Sim3Solver *s, double *e, double *J);
 int sim3_get_last_step(const Sim3Solver *s, int prob, double *H, double *b, double *dx);
 
+// Batched Sim3 RANSAC (sqlm_sim3_ransac.cpp host, sqlm_sim3_ransac.hip kernel):
+// every hypothesis of every problem in one launch, a wavefront per hypothesis.
+constexpr int kRansacWaves = 4;       // wavefronts of a workgroup
+constexpr int kRansacHypPerWave = 2;  // hypotheses a wavefront loops over
+constexpr int kRansacHypPerWg = kRansacWaves * kRansacHypPerWave;
+struct RansacProb {  // one problem of the batch, as the kernel reads it
+  float K1[4], K2[4];
+  int32_t pair0, n_pair;  // its pairs in the pair arrays
+  int32_t hyp0, n_hyp;    // its hypotheses in the per-hypothesis arrays
+  int64_t mask0;          // its first mask word; hypothesis h owns (n_pair + 63) / 64 words
+  int32_t fix_scale, pad;
+};
+struct RansacDev {  // device pointers of one sqlm_sim3_ransac call
+  int n_wg = 0;
+  const RansacProb *prob = nullptr;                      // [n_prob]
+  const int32_t *wg_prob = nullptr, *wg_hyp = nullptr;   // [n_wg] problem and first hypothesis (batch index) of a workgroup
+  const float *X1c = nullptr, *X2c = nullptr;            // [n_pair][3]
+  const int32_t *max_err1 = nullptr, *max_err2 = nullptr;  // [n_pair]
+  const int32_t *draws = nullptr;                        // [n_hyp][3]
+  int32_t *count = nullptr, *idx = nullptr;              // [n_hyp], [n_hyp][3]
+  float *hyp = nullptr;                                  // [n_hyp][kRansacHypFloats]
+  unsigned long long *mask = nullptr;                    // inlier bits, 64 pairs a word
+};
+void launch_sim3_ransac(const RansacDev &d, hipStream_t st);
+struct RansacSolver;
+RansacSolver *ransac_create(hipStream_t st);
+void ransac_destroy(RansacSolver *s);
+struct RansacArgs {  // host pointers of one call (see include/sqrtlm.h)
+  int n_prob = 0;
+  const double *intr1 = nullptr, *intr2 = nullptr;
+  const uint8_t *fix_scale = nullptr;
+  const int32_t *min_inliers = nullptr;
+  const int64_t *pair_off = nullptr;
+  const double *X1c = nullptr, *X2c = nullptr;
+  const int32_t *max_err1 = nullptr, *max_err2 = nullptr;
+  const int64_t *hyp_off = nullptr;
+  const int32_t *draws = nullptr;
+  int32_t *n_inliers = nullptr;
+  uint8_t *flags = nullptr;
+  float *R12 = nullptr, *t12 = nullptr, *s12 = nullptr;
+  int32_t *first_return = nullptr, *best = nullptr;
+};
+int ransac_args_ok(const RansacArgs &a);
+int ransac_run(RansacSolver *s, const RansacArgs &a);
+int ransac_get_inliers(const RansacSolver *s, int prob, int hyp, uint8_t *mask);
+int ransac_get_hypothesis(const RansacSolver *s, int prob, int hyp, int32_t *idx, float *T12, float *T21);
+int ransac_hypothesis_host(int n_pair, const double *intr1, const double *intr2, int fix_scale, const double *X1c,
+                           const double *X2c, const int32_t *max_err1, const int32_t *max_err2, const int32_t *draws,
+                           int32_t *idx, float *hyp /* [34] RansacHyp */, uint8_t *mask, int32_t *count);
+int ransac_max_its(int64_t n_pair, double probability, int min_inliers, int max_iterations);
+void ransac_scan(int64_t n_hyp, const int32_t *counts, int min_inliers, uint8_t *flags, int64_t *first_return,
+                 int64_t *best);
+
 // Batched motion-only BA (sqlm_pose.cpp host, sqlm_pose.hip kernel): one
 // solver per context, on the context's stream; its buffers are reused.
 constexpr int kPoseChecks = 5;   // 4 rounds + the final classification

@@ -51,6 +51,9 @@ EXPORTS = [
     # int sqlm_set_lidar_from_cloud_sets(ctx, int32_t pose_index, int n_sets, const sqlm_lidar_set *sets,
     #     int64_t *n_pairs /* [n_sets] */)
     "sqlm_set_lidar_kind", "sqlm_set_lidar_from_cloud_sets",
+    # Sim3 RANSAC (Sim3Solver): every hypothesis of every candidate in one launch, and its host-only helpers
+    "sqlm_sim3_ransac", "sqlm_sim3_ransac_get_inliers", "sqlm_sim3_ransac_get_hypothesis",
+    "sqlm_sim3_ransac_max_its", "sqlm_sim3_ransac_scan", "sqlm_sim3_ransac_hypothesis_host",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -179,6 +182,18 @@ def lib() -> C.CDLL:
             L.sqlm_bow_transform.argtypes = [P, P, C.c_int, P, P, C.c_int, P, P, P, P, P]
             # ctx, nq, q_word, q_value, n_db, db_off, db_word, db_value, score, n_common
             L.sqlm_bow_score.argtypes = [P, C.c_int64, P, P, C.c_int, P, P, P, P, P]
+        if hasattr(L, "sqlm_sim3_ransac"):
+            P = C.c_void_p
+            # ctx, n_prob, intr1, intr2, fix_scale, min_inliers, pair_off, X1c, X2c, max_err1, max_err2, hyp_off,
+            # draws, n_inliers, flags, R12, t12, s12, first_return, best
+            L.sqlm_sim3_ransac.argtypes = [P, C.c_int] + [P] * 18
+            L.sqlm_sim3_ransac_get_inliers.argtypes = [P, C.c_int, C.c_int, P]
+            L.sqlm_sim3_ransac_get_hypothesis.argtypes = [P, C.c_int, C.c_int, P, P, P]
+            L.sqlm_sim3_ransac_max_its.argtypes = [C.c_int64, C.c_double, C.c_int, C.c_int]
+            L.sqlm_sim3_ransac_scan.argtypes = [C.c_int64, P, C.c_int, P, P, P]
+            # n_pair, intr1, intr2, fix_scale, X1c, X2c, max_err1, max_err2, draws, idx, R12, t12, s12, T12, T21,
+            # mask, n_inliers
+            L.sqlm_sim3_ransac_hypothesis_host.argtypes = [C.c_int, P, P, C.c_int] + [P] * 13
         _lib = L
     return _lib
 

@@ -12,6 +12,9 @@ schedule on the MI355X through libsqrtlm.so:
 * ``PoseOptimization``       -> g2oOptimizer.cc:385-679 (batched: ``Context.pose_optimize`` /
   ``Context.pose_refine_lidar``)
 
+The RANSAC in front of ``OptimizeSim3`` (src/algorithm/Sim3Solver.cc) is
+``sim3.Sim3Solver`` over ``Context.sim3_ransac``.
+
 Results are written back into the problem (poses, points) like the
 reference's ``SetPose`` / ``SetWorldPos`` write-back (g2oOptimizer.cc:1167-1189).
 """
@@ -329,6 +332,45 @@ class Context:
         H, b, dx = np.zeros((7, 7)), np.zeros(7), np.zeros(7)
         check(lib().sqlm_sim3_get_last_step(self._h, int(prob), ptr(H), ptr(b), ptr(dx)), "sqlm_sim3_get_last_step")
         return H, b, dx
+
+    # ------------------------------------------------------------- Sim3 RANSAC
+    def sim3_ransac(self, problems, draws, max_err, min_inliers=6):
+        """sqlm_sim3_ransac on a list of sim3.Sim3Problem: every hypothesis of
+        every problem in one launch. ``draws``: one (n_hyp, 3) array of raw
+        RandomInt values per problem; ``max_err``: one (max_err1, max_err2)
+        per problem, as stored (truncated); ``min_inliers``: an int or one per
+        problem. Returns one dict per problem: n_inliers (H,), flags (H,),
+        R12 (H,3,3), t12 (H,3), s12 (H,) float32, first_return, best."""
+        from . import sim3 as _s3
+        a = _s3.pack_ransac(problems, max_err, draws, min_inliers)
+        P, H = len(problems), int(a["hyp_off"][-1])
+        n_in, flags = np.zeros(H, np.int32), np.zeros(H, np.uint8)
+        R, t, s = np.zeros((H, 3, 3), np.float32), np.zeros((H, 3), np.float32), np.zeros(H, np.float32)
+        first, best = np.zeros(P, np.int32), np.zeros(P, np.int32)
+        check(lib().sqlm_sim3_ransac(
+            self._h, P, ptr(a["intr1"]), ptr(a["intr2"]), ptr(a["fix_scale"]), ptr(a["min_inliers"]),
+            ptr(a["pair_off"]), ptr(a["X1c"]), ptr(a["X2c"]), ptr(a["max_err1"]), ptr(a["max_err2"]),
+            ptr(a["hyp_off"]), ptr(a["draws"]), ptr(n_in), ptr(flags), ptr(R), ptr(t), ptr(s), ptr(first), ptr(best)),
+            "sqlm_sim3_ransac")
+        self.sim3_ransac_pairs = np.diff(a["pair_off"])
+        o = a["hyp_off"]
+        return [dict(n_inliers=n_in[o[k]:o[k + 1]], flags=flags[o[k]:o[k + 1]], R12=R[o[k]:o[k + 1]],
+                     t12=t[o[k]:o[k + 1]], s12=s[o[k]:o[k + 1]], first_return=int(first[k]), best=int(best[k]))
+                for k in range(P)]
+
+    def sim3_ransac_inliers(self, prob: int, hyp: int):
+        """mvbInliersi (N,) uint8 of hypothesis ``hyp`` of problem ``prob`` of the last sim3_ransac."""
+        mask = np.zeros(max(int(self.sim3_ransac_pairs[prob]), 1), np.uint8)
+        check(lib().sqlm_sim3_ransac_get_inliers(self._h, int(prob), int(hyp), ptr(mask)),
+              "sqlm_sim3_ransac_get_inliers")
+        return mask[:int(self.sim3_ransac_pairs[prob])]
+
+    def sim3_ransac_hypothesis(self, prob: int, hyp: int):
+        """(idx (3,), T12 (4,4), T21 (4,4) float32): the pairs hypothesis ``hyp`` drew and the transforms CheckInliers used."""
+        idx, T12, T21 = np.zeros(3, np.int32), np.zeros((4, 4), np.float32), np.zeros((4, 4), np.float32)
+        check(lib().sqlm_sim3_ransac_get_hypothesis(self._h, int(prob), int(hyp), ptr(idx), ptr(T12), ptr(T21)),
+              "sqlm_sim3_ransac_get_hypothesis")
+        return idx, T12, T21
 
     # ------------------------------------------------------------- motion-only BA
     def _pose_out(self, a, P):

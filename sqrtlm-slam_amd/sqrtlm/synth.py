@@ -586,6 +586,12 @@ def make_sim3_problem(*args, **kw):
     return make(*args, **kw)
 
 
+def make_sim3_ransac_problem(*args, **kw):
+    """A loop candidate with mismatched pairs for the Sim3 RANSAC: see sim3.make_sim3_ransac_problem."""
+    from .sim3 import make_sim3_ransac_problem as make
+    return make(*args, **kw)
+
+
 def make_pose_problem(*args, **kw):
     """Map points seen by one frame with a known pose for PoseOptimization: see pose.make_pose_problem."""
     from .pose import make_pose_problem as make
