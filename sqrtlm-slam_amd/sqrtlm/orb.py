@@ -162,6 +162,19 @@ class BowFrame:
         return b
 
 
+def _image_rows(image):
+    """(uint8 image, row stride in bytes) as sqlm_orb_extract takes it: a 2-D
+    uint8 array whose elements are adjacent in a row and whose rows are at
+    least a row apart is passed as it is (a view into a wider buffer keeps its
+    stride); anything else is copied to contiguous."""
+    img = np.asarray(image)
+    if img.ndim != 2:
+        raise ValueError("ORBextractor expects a CV_8UC1 image")
+    if img.dtype != np.uint8 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+        img = np.ascontiguousarray(img, np.uint8)
+    return img, int(img.strides[0])
+
+
 class ORBextractor:
     """ORBextractor(nfeatures, scaleFactor, nlevels, iniThFAST, minThFAST)
     (ORBextractor.cc:474-560). ``extractor(image)`` is operator()
@@ -181,17 +194,15 @@ class ORBextractor:
         self.mvInvLevelSigma2 = (np.float32(1.0) / self.mvLevelSigma2).astype(np.float32)
 
     def __call__(self, image: np.ndarray):
-        img = np.ascontiguousarray(image, np.uint8)
-        if img.ndim != 2:
-            raise ValueError("ORBextractor expects a CV_8UC1 image")
+        img, stride = _image_rows(image)
         h, w = img.shape
         cap = max(64, 2 * int(self.params.nfeatures))
         while True:
             kps = np.zeros(cap, KP_DTYPE)
             desc = np.zeros((cap, 32), np.uint8)
             n = C.c_int(0)
-            check(lib().sqlm_orb_extract(self.ctx._h, C.byref(self.params), ptr(img), w, h, w, ptr(kps), ptr(desc),
-                                         cap, C.byref(n)), "sqlm_orb_extract")
+            check(lib().sqlm_orb_extract(self.ctx._h, C.byref(self.params), ptr(img), w, h, stride, ptr(kps),
+                                         ptr(desc), cap, C.byref(n)), "sqlm_orb_extract")
             if n.value <= cap:
                 return kps[:n.value], desc[:n.value]
             cap = n.value
@@ -229,11 +240,11 @@ class ORBextractor:
 
     def bench(self, image: np.ndarray, reps: int = 50):
         """(ms per frame, stage ms [pyramid, fast, compact, blur, describe, host quadtree])."""
-        img = np.ascontiguousarray(image, np.uint8)
+        img, stride = _image_rows(image)
         ms = C.c_double(0)
         st = (C.c_double * 6)()
         check(lib().sqlm_orb_bench_extract(self.ctx._h, C.byref(self.params), ptr(img), img.shape[1], img.shape[0],
-                                           img.shape[1], int(reps), C.byref(ms), st), "sqlm_orb_bench_extract")
+                                           stride, int(reps), C.byref(ms), st), "sqlm_orb_bench_extract")
         return ms.value, list(st)
 
     def close(self):
