@@ -286,6 +286,88 @@ int sqlm_sim3_ransac_hypothesis_host(int n_pair, const double intr1[4], const do
     int32_t idx[3], float R12[9], float t12[3], float *s12, float T12[16], float T21[16], uint8_t *mask,
     int32_t *n_inliers);
 
+/* PnP RANSAC of relocalization candidates: PnPsolver
+ * (src/algorithm/PnPsolver.cc), EPnP inside RANSAC, every hypothesis of n_prob
+ * candidates in one launch and the Refine() of the record-breaking ones in a
+ * second. A problem's pairs are the correspondences the constructor keeps
+ * (:131-153): Xw the float world position, uv the undistorted keypoint, max_err
+ * mvMaxError as stored (the float product mvSigma2 * th2, :226); intr is fu fv
+ * uc vc. Hypothesis h of a problem with N pairs uses draws[h][0..3], the raw
+ * DUtils::Random::RandomInt(0, size-1) values of :286, draws[h][i] in
+ * [0, N-1-i]; the library maps them to pair indices as the swap-remove of
+ * :281-297 does. Per hypothesis: compute_pose on the four points and
+ * CheckInliers (:430-467) in the precisions written there. The scalar code of
+ * EPnP is the reference's in double; what it hands to OpenCV is the library's
+ * own, deterministic definition: fixed-sweep cyclic Jacobi for
+ * the two symmetric eigenproblems, the inverse of CC from its orthogonal
+ * columns, the reference's qr_solve for the 6x4, 6x3 and 6x5 systems, a
+ * one-sided Jacobi SVD for R = U V^T. A NaN or Inf pose has 0 inliers.
+ * Then, per problem, the bookkeeping of iterate() (:308-344) over the counts
+ * c_h with a running best b (initially 0): flags[h] bit 0 = it qualifies
+ * (c_h >= min_inliers), bit 1 = it is also a new best (c_h > b; a "record"),
+ * bit 2 = it returns: it qualifies and the Refine() of the best mask so far,
+ * i.e. of the latest record, found more than min_inliers inliers. first_return
+ * is the first returning hypothesis or -1, best the last record or -1; both
+ * count from the problem's first hypothesis. Tcw / n_refined are mRefinedTcw
+ * (4x4 row-major float) and mnRefinedInliers at first_return (identity and 0
+ * without one). A problem with hypotheses and fewer than 4 or fewer than
+ * min_inliers pairs, or a draw out of range, is SQLM_ERR_INVALID_ARG. */
+int sqlm_pnp_ransac(sqlm_ctx *ctx, int n_prob,
+    const double *intr,           /* [n_prob][4] fu fv uc vc                                           */
+    const int32_t *min_inliers,   /* [n_prob] mRansacMinInliers after SetRansacParameters              */
+    const int64_t *pair_off,      /* [n_prob+1] CSR offsets into the pair arrays                       */
+    const float *Xw,              /* [n_pair][3]                                                       */
+    const float *uv,              /* [n_pair][2]                                                       */
+    const float *max_err,         /* [n_pair]                                                          */
+    const int64_t *hyp_off,       /* [n_prob+1] CSR offsets into the per-hypothesis arrays             */
+    const int32_t *draws,         /* [n_hyp][4]                                                        */
+    int32_t *n_inliers,           /* [n_hyp] mnInliersi                                                */
+    uint8_t *flags,               /* [n_hyp]                                                           */
+    double *R, double *t,         /* [n_hyp][9] row-major, [n_hyp][3]: mRi, mti                        */
+    int32_t *first_return, int32_t *best,       /* [n_prob]                                           */
+    float *Tcw, int32_t *n_refined);            /* [n_prob][16], [n_prob]                             */
+/* Of the last sqlm_pnp_ransac of the context (SQLM_ERR_STATE before any):
+ * mvbInliersi of hypothesis `hyp` of problem `prob`, mask [N] of 0 / 1; the
+ * Refine() of a record's mask (SQLM_ERR_STATE for a hypothesis that is no
+ * record: the reference never refines its mask); and diagnostics of a
+ * hypothesis: the four pair indices, the 12x12 ut (rows by descending
+ * eigenvalue) with its eigenvalues, the three beta vectors after Gauss-Newton
+ * (the reference's N = 4, 2, 3 order), their reprojection errors and the
+ * chosen candidate 0..2. Any output pointer but mask of get_inliers may be NULL. */
+int sqlm_pnp_ransac_get_inliers(sqlm_ctx *ctx, int prob, int hyp, uint8_t *mask);
+int sqlm_pnp_ransac_get_refined(sqlm_ctx *ctx, int prob, int hyp, double R[9], double t[3], uint8_t *mask,
+    int32_t *n_inliers, double ut[144], double eig[12], double betas[12], double rep_err[3], int32_t *chosen);
+int sqlm_pnp_ransac_get_hypothesis(sqlm_ctx *ctx, int prob, int hyp, int32_t idx[4], double ut[144], double eig[12],
+    double betas[12], double rep_err[3], int32_t *chosen);
+/* Host only, no context. SetRansacParameters(probability, min_inliers,
+ * max_iterations, min_set, epsilon, .) on n_pair correspondences (:178-227):
+ * *min_inliers_out = max((int)(n_pair * epsilon) as a float product,
+ * min_inliers, min_set); the return value is mRansacMaxIts = max(1,
+ * min(ceil(log(1-p) / log(1 - pow(max(epsilon, (float)that / n_pair), 3))),
+ * max_iterations)), clamped in double before the conversion to int; 1 if that
+ * count == n_pair; 0 if n_pair is below it, where iterate() gives up at once
+ * (:257-261). */
+int sqlm_pnp_ransac_max_its(int64_t n_pair, double probability, int min_inliers, int max_iterations, int min_set,
+    float epsilon, int *min_inliers_out);
+/* Host only: the bookkeeping above on given counts. refined[0 .. n_refined)
+ * are the refined inlier counts of the records in their order; a record past
+ * them (or refined == NULL) counts as a failed refine. flags, first_return,
+ * best and n_record (the number of records) may be NULL. */
+int sqlm_pnp_ransac_scan(int64_t n_hyp, const int32_t *counts, const int32_t *refined, int64_t n_refined,
+    int min_inliers, uint8_t *flags, int64_t *first_return, int64_t *best, int64_t *n_record);
+/* Host only: one hypothesis and one refine (EPnP on the pairs with in_mask != 0,
+ * then CheckInliers) of one problem on the CPU by the source text the kernels
+ * are compiled from. sweeps, if not NULL, replaces the Jacobi sweep counts of
+ * the 3x3, the 12x12 and the polar factor where > 0 (the CPU test that keeps
+ * the library's counts converged). The diagnostic outputs may be NULL. */
+int sqlm_pnp_ransac_hypothesis_host(int n_pair, const double intr[4], const float *Xw, const float *uv,
+    const float *max_err, const int32_t draws[4], const int32_t sweeps[3], int32_t idx[4], double R[9], double t[3],
+    uint8_t *mask, int32_t *n_inliers, double ut[144], double eig[12], double betas[12], double rep_err[3],
+    int32_t *chosen);
+int sqlm_pnp_ransac_refine_host(int n_pair, const double intr[4], const float *Xw, const float *uv,
+    const float *max_err, const uint8_t *in_mask, const int32_t sweeps[3], double R[9], double t[3], uint8_t *mask,
+    int32_t *n_inliers, double ut[144], double eig[12], double betas[12], double rep_err[3], int32_t *chosen);
+
 /* Motion-only bundle adjustment: g2oOptimizer::PoseOptimization
  * (g2oOptimizer.cc:385-679), n_prob independent problems in one call (Tracking's
  * call is n_prob = 1, Relocalization's candidates are a batch). One free

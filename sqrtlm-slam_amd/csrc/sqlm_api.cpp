@@ -146,6 +146,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   if (c->eg) eg_destroy(c->eg);
   if (c->sim3) sim3_destroy(c->sim3);
   if (c->ransac) ransac_destroy(c->ransac);
+  if (c->pnp) pnp_destroy(c->pnp);
   if (c->pose) pose_destroy(c->pose);
   if (c->lidar) lidar_destroy(c->lidar);
   if (c->orb) orb_destroy(c->orb);
@@ -485,6 +486,102 @@ int sqlm_sim3_ransac_hypothesis_host(int n_pair, const double intr1[4], const do
       T12[4 * i + j] = i == 3 ? (j == 3 ? 1.f : 0.f) : (j == 3 ? h[9 + i] : h[13 + 3 * i + j]);
       T21[4 * i + j] = i == 3 ? (j == 3 ? 1.f : 0.f) : (j == 3 ? h[31 + i] : h[22 + 3 * i + j]);
     }
+  return SQLM_OK;
+}
+
+namespace {
+
+// the diagnostics of a PnP solve (kPnpDiag doubles) into the ABI's separate arrays
+void pnp_split_diag(const double *d, double *ut, double *eig, double *betas, double *rep, int32_t *chosen) {
+  if (ut) std::memcpy(ut, d, 144 * sizeof(double));
+  if (eig) std::memcpy(eig, d + 144, 12 * sizeof(double));
+  if (betas) std::memcpy(betas, d + 156, 12 * sizeof(double));
+  if (rep) std::memcpy(rep, d + 168, 3 * sizeof(double));
+  if (chosen) *chosen = (int32_t)d[171];
+}
+
+}  // namespace
+
+int sqlm_pnp_ransac(sqlm_ctx *c, int n_prob, const double *intr, const int32_t *min_inliers, const int64_t *pair_off,
+                    const float *Xw, const float *uv, const float *max_err, const int64_t *hyp_off,
+                    const int32_t *draws, int32_t *n_inliers, uint8_t *flags, double *R, double *t,
+                    int32_t *first_return, int32_t *best, float *Tcw, int32_t *n_refined) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  PnpArgs a;
+  a.n_prob = n_prob;
+  a.intr = intr; a.min_inliers = min_inliers; a.pair_off = pair_off; a.Xw = Xw; a.uv = uv; a.max_err = max_err;
+  a.hyp_off = hyp_off; a.draws = draws; a.n_inliers = n_inliers; a.flags = flags; a.R = R; a.t = t;
+  a.first_return = first_return; a.best = best; a.Tcw = Tcw; a.n_refined = n_refined;
+  if (int r = pnp_args_ok(a)) return r;
+  if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  if (!c->pnp && !(c->pnp = pnp_create(c->stream))) return SQLM_ERR_OOM;
+  return pnp_run(c->pnp, a);
+}
+
+int sqlm_pnp_ransac_get_inliers(sqlm_ctx *c, int prob, int hyp, uint8_t *mask) {
+  if (!c || !mask) return SQLM_ERR_INVALID_ARG;
+  if (!c->pnp) return SQLM_ERR_STATE;
+  return pnp_get_inliers(c->pnp, prob, hyp, mask);
+}
+
+int sqlm_pnp_ransac_get_refined(sqlm_ctx *c, int prob, int hyp, double R[9], double t[3], uint8_t *mask,
+                                int32_t *n_inliers, double ut[144], double eig[12], double betas[12],
+                                double rep_err[3], int32_t *chosen) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  if (!c->pnp) return SQLM_ERR_STATE;
+  double d[kPnpDiag];
+  if (int r = pnp_get_refined(c->pnp, prob, hyp, R, t, mask, n_inliers, d)) return r;
+  pnp_split_diag(d, ut, eig, betas, rep_err, chosen);
+  return SQLM_OK;
+}
+
+int sqlm_pnp_ransac_get_hypothesis(sqlm_ctx *c, int prob, int hyp, int32_t idx[4], double ut[144], double eig[12],
+                                   double betas[12], double rep_err[3], int32_t *chosen) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  if (!c->pnp) return SQLM_ERR_STATE;
+  const bool want = ut || eig || betas || rep_err || chosen;
+  if (want && hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+  double d[kPnpDiag];
+  if (int r = pnp_get_hypothesis(c->pnp, prob, hyp, idx, want ? d : nullptr)) return r;
+  if (want) pnp_split_diag(d, ut, eig, betas, rep_err, chosen);
+  return SQLM_OK;
+}
+
+int sqlm_pnp_ransac_max_its(int64_t n_pair, double probability, int min_inliers, int max_iterations, int min_set,
+                            float epsilon, int *min_inliers_out) {
+  if (n_pair < 0 || n_pair > INT32_MAX) return 0;
+  return pnp_max_its(n_pair, probability, min_inliers, max_iterations, min_set, epsilon, min_inliers_out);
+}
+
+int sqlm_pnp_ransac_scan(int64_t n_hyp, const int32_t *counts, const int32_t *refined, int64_t n_refined,
+                         int min_inliers, uint8_t *flags, int64_t *first_return, int64_t *best, int64_t *n_record) {
+  if (n_hyp < 0 || n_refined < 0 || (n_hyp > 0 && !counts)) return SQLM_ERR_INVALID_ARG;
+  pnp_scan(n_hyp, counts, refined, n_refined, min_inliers, flags, first_return, best, n_record);
+  return SQLM_OK;
+}
+
+int sqlm_pnp_ransac_hypothesis_host(int n_pair, const double intr[4], const float *Xw, const float *uv,
+                                    const float *max_err, const int32_t draws[4], const int32_t sweeps[3],
+                                    int32_t idx[4], double R[9], double t[3], uint8_t *mask, int32_t *n_inliers,
+                                    double ut[144], double eig[12], double betas[12], double rep_err[3],
+                                    int32_t *chosen) {
+  if (!intr || !Xw || !uv || !max_err || !draws || !idx || !R || !t || !mask || !n_inliers)
+    return SQLM_ERR_INVALID_ARG;
+  double d[kPnpDiag];
+  if (int r = pnp_hypothesis_host(n_pair, intr, Xw, uv, max_err, draws, sweeps, idx, R, t, mask, n_inliers, d))
+    return r;
+  pnp_split_diag(d, ut, eig, betas, rep_err, chosen);
+  return SQLM_OK;
+}
+
+int sqlm_pnp_ransac_refine_host(int n_pair, const double intr[4], const float *Xw, const float *uv,
+                                const float *max_err, const uint8_t *in_mask, const int32_t sweeps[3], double R[9],
+                                double t[3], uint8_t *mask, int32_t *n_inliers, double ut[144], double eig[12],
+                                double betas[12], double rep_err[3], int32_t *chosen) {
+  if (!intr || !Xw || !uv || !max_err || !in_mask || !R || !t || !mask || !n_inliers) return SQLM_ERR_INVALID_ARG;
+  double d[kPnpDiag];
+  if (int r = pnp_refine_host(n_pair, intr, Xw, uv, max_err, in_mask, sweeps, R, t, mask, n_inliers, d)) return r;
+  pnp_split_diag(d, ut, eig, betas, rep_err, chosen);
   return SQLM_OK;
 }
 

@@ -95,6 +95,7 @@ struct sqlm_ctx {
   sqlm::EGSolver *eg = nullptr;
   sqlm::Sim3Solver *sim3 = nullptr;
   sqlm::RansacSolver *ransac = nullptr;  // sqlm_sim3_ransac (sqlm_sim3_ransac.cpp)
+  sqlm::PnpSolver *pnp = nullptr;  // sqlm_pnp_ransac (sqlm_pnp_ransac.cpp)
   sqlm::PoseSolver *pose = nullptr;
   sqlm::LidarSolver *lidar = nullptr;
   sqlm::OrbEngine *orb = nullptr;

@@ -536,6 +536,76 @@ int ransac_max_its(int64_t n_pair, double probability, int min_inliers, int max_
 void ransac_scan(int64_t n_hyp, const int32_t *counts, int min_inliers, uint8_t *flags, int64_t *first_return,
                  int64_t *best);
 
+// Batched PnP RANSAC (sqlm_pnp_ransac.cpp host, sqlm_pnp_ransac.hip kernels):
+// k_pnp_hyp evaluates every hypothesis of every problem, a wavefront per
+// hypothesis; k_pnp_refine re-solves EPnP on the inliers of the record-breaking
+// hypotheses the host scan found, a wavefront per record.
+constexpr int kPnpWaves = 4;  // wavefronts of a k_pnp_hyp workgroup, one hypothesis each
+constexpr int kPnpHypPerWg = kPnpWaves;
+constexpr int kPnpPose = 12;   // doubles of a stored pose: R 9, t 3
+constexpr int kPnpDiag = 172;  // doubles of the diagnostics: ut 144, eigenvalues 12, betas 3x4, errors 3, candidate
+struct PnpProb {  // one problem of the batch, as the kernels read it
+  double K[4];            // fu fv uc vc
+  int32_t pair0, n_pair;  // its pairs in the pair arrays
+  int32_t hyp0, n_hyp;    // its hypotheses in the per-hypothesis arrays
+  int64_t mask0;          // its first mask word; hypothesis h owns (n_pair + 63) / 64 words
+};
+struct PnpDev {  // device pointers of one sqlm_pnp_ransac call
+  const PnpProb *prob = nullptr;                           // [n_prob]
+  const float *Xw = nullptr, *uv = nullptr, *max_err = nullptr;  // [n_pair][3], [n_pair][2], [n_pair]
+  // k_pnp_hyp
+  int n_wg = 0;
+  const int32_t *wg_prob = nullptr, *wg_hyp = nullptr;  // [n_wg] problem and first hypothesis (batch index) of a workgroup
+  const int32_t *draws = nullptr;                       // [n_hyp][4]
+  int32_t *count = nullptr, *idx = nullptr;             // [n_hyp], [n_hyp][4]
+  double *pose = nullptr, *diag = nullptr;              // [n_hyp][kPnpPose], [n_hyp][kPnpDiag]
+  unsigned long long *mask = nullptr;                   // inlier bits, 64 pairs a word
+  // k_pnp_refine
+  int n_rec = 0;
+  const int32_t *rec_prob = nullptr, *rec_hyp = nullptr;  // [n_rec] problem and hypothesis (batch index) of a record
+  const int64_t *rec_list0 = nullptr, *rec_mask0 = nullptr;  // [n_rec] its first list entry and refined mask word
+  int32_t *list = nullptr;                                // the inlier indices of a record, ascending
+  int32_t *rcount = nullptr;                              // [n_rec]
+  double *rpose = nullptr, *rdiag = nullptr;              // [n_rec][kPnpPose], [n_rec][kPnpDiag]
+  unsigned long long *rmask = nullptr;
+};
+void launch_pnp_hyp(const PnpDev &d, hipStream_t st);
+void launch_pnp_refine(const PnpDev &d, hipStream_t st);
+struct PnpSolver;
+PnpSolver *pnp_create(hipStream_t st);
+void pnp_destroy(PnpSolver *s);
+struct PnpArgs {  // host pointers of one call (see include/sqrtlm.h)
+  int n_prob = 0;
+  const double *intr = nullptr;
+  const int32_t *min_inliers = nullptr;
+  const int64_t *pair_off = nullptr;
+  const float *Xw = nullptr, *uv = nullptr, *max_err = nullptr;
+  const int64_t *hyp_off = nullptr;
+  const int32_t *draws = nullptr;
+  int32_t *n_inliers = nullptr;
+  uint8_t *flags = nullptr;
+  double *R = nullptr, *t = nullptr;
+  int32_t *first_return = nullptr, *best = nullptr;
+  float *Tcw = nullptr;
+  int32_t *n_refined = nullptr;
+};
+int pnp_args_ok(const PnpArgs &a);
+int pnp_run(PnpSolver *s, const PnpArgs &a);
+int pnp_get_inliers(const PnpSolver *s, int prob, int hyp, uint8_t *mask);
+int pnp_get_refined(PnpSolver *s, int prob, int hyp, double *R, double *t, uint8_t *mask, int32_t *n_inliers,
+                    double *diag /* [kPnpDiag] or null */);
+int pnp_get_hypothesis(PnpSolver *s, int prob, int hyp, int32_t *idx, double *diag /* [kPnpDiag] or null */);
+int pnp_hypothesis_host(int n_pair, const double *intr, const float *Xw, const float *uv, const float *max_err,
+                        const int32_t *draws, const int32_t *sweeps, int32_t *idx, double *R, double *t,
+                        uint8_t *mask, int32_t *count, double *diag);
+int pnp_refine_host(int n_pair, const double *intr, const float *Xw, const float *uv, const float *max_err,
+                    const uint8_t *in_mask, const int32_t *sweeps, double *R, double *t, uint8_t *mask,
+                    int32_t *count, double *diag);
+int pnp_max_its(int64_t n_pair, double probability, int min_inliers, int max_iterations, int min_set, float epsilon,
+                int *min_inliers_out);
+void pnp_scan(int64_t n_hyp, const int32_t *counts, const int32_t *refined, int64_t n_refined, int min_inliers,
+              uint8_t *flags, int64_t *first_return, int64_t *best, int64_t *n_record);
+
 // Batched motion-only BA (sqlm_pose.cpp host, sqlm_pose.hip kernel): one
 // solver per context, on the context's stream; its buffers are reused.
 constexpr int kPoseChecks = 5;   // 4 rounds + the final classification

@@ -54,6 +54,10 @@ EXPORTS = [
     # Sim3 RANSAC (Sim3Solver): every hypothesis of every candidate in one launch, and its host-only helpers
     "sqlm_sim3_ransac", "sqlm_sim3_ransac_get_inliers", "sqlm_sim3_ransac_get_hypothesis",
     "sqlm_sim3_ransac_max_its", "sqlm_sim3_ransac_scan", "sqlm_sim3_ransac_hypothesis_host",
+    # PnP RANSAC (PnPsolver): every hypothesis of every candidate in one launch, the refines in a second
+    "sqlm_pnp_ransac", "sqlm_pnp_ransac_get_inliers", "sqlm_pnp_ransac_get_refined", "sqlm_pnp_ransac_get_hypothesis",
+    "sqlm_pnp_ransac_max_its", "sqlm_pnp_ransac_scan", "sqlm_pnp_ransac_hypothesis_host",
+    "sqlm_pnp_ransac_refine_host",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -194,6 +198,23 @@ def lib() -> C.CDLL:
             # n_pair, intr1, intr2, fix_scale, X1c, X2c, max_err1, max_err2, draws, idx, R12, t12, s12, T12, T21,
             # mask, n_inliers
             L.sqlm_sim3_ransac_hypothesis_host.argtypes = [C.c_int, P, P, C.c_int] + [P] * 13
+        if hasattr(L, "sqlm_pnp_ransac"):
+            P = C.c_void_p
+            # ctx, n_prob, intr, min_inliers, pair_off, Xw, uv, max_err, hyp_off, draws, n_inliers, flags, R, t,
+            # first_return, best, Tcw, n_refined
+            L.sqlm_pnp_ransac.argtypes = [P, C.c_int] + [P] * 16
+            L.sqlm_pnp_ransac_get_inliers.argtypes = [P, C.c_int, C.c_int, P]
+            # ctx, prob, hyp, R, t, mask, n_inliers, ut, eig, betas, rep_err, chosen
+            L.sqlm_pnp_ransac_get_refined.argtypes = [P, C.c_int, C.c_int] + [P] * 9
+            # ctx, prob, hyp, idx, ut, eig, betas, rep_err, chosen
+            L.sqlm_pnp_ransac_get_hypothesis.argtypes = [P, C.c_int, C.c_int] + [P] * 6
+            L.sqlm_pnp_ransac_max_its.argtypes = [C.c_int64, C.c_double, C.c_int, C.c_int, C.c_int, C.c_float, P]
+            # n_hyp, counts, refined, n_refined, min_inliers, flags, first_return, best, n_record
+            L.sqlm_pnp_ransac_scan.argtypes = [C.c_int64, P, P, C.c_int64, C.c_int, P, P, P, P]
+            # n_pair, intr, Xw, uv, max_err, draws | in_mask, sweeps, [idx,] R, t, mask, n_inliers, ut, eig, betas,
+            # rep_err, chosen
+            L.sqlm_pnp_ransac_hypothesis_host.argtypes = [C.c_int] + [P] * 16
+            L.sqlm_pnp_ransac_refine_host.argtypes = [C.c_int] + [P] * 15
         _lib = L
     return _lib
 

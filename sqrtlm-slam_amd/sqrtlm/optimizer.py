@@ -372,6 +372,68 @@ class Context:
               "sqlm_sim3_ransac_get_hypothesis")
         return idx, T12, T21
 
+    # ------------------------------------------------------------- PnP RANSAC
+    def pnp_ransac(self, problems, draws, min_inliers, max_err=None):
+        """sqlm_pnp_ransac on a list of pnp.PnPProblem: every hypothesis of
+        every problem in one launch, the refines of the record-breaking ones in
+        a second. ``draws``: one (n_hyp, 4) array of raw RandomInt values per
+        problem; ``min_inliers``: mRansacMinInliers, an int or one per problem;
+        ``max_err``: one (N,) float32 array per problem (default: the
+        problem's sigma2 * 5.991). Returns one dict per problem: n_inliers
+        (H,), flags (H,), R (H,3,3), t (H,3) float64, first_return, best, Tcw
+        (4,4) float32, n_refined."""
+        from . import pnp as _pnp
+        a = _pnp.pack(problems, draws, min_inliers, max_err)
+        P, H = len(problems), int(a["hyp_off"][-1])
+        n_in, flags = np.zeros(H, np.int32), np.zeros(H, np.uint8)
+        R, t = np.zeros((H, 3, 3)), np.zeros((H, 3))
+        first, best, n_ref = np.zeros(P, np.int32), np.zeros(P, np.int32), np.zeros(P, np.int32)
+        Tcw = np.zeros((P, 4, 4), np.float32)
+        check(lib().sqlm_pnp_ransac(
+            self._h, P, ptr(a["intr"]), ptr(a["min_inliers"]), ptr(a["pair_off"]), ptr(a["Xw"]), ptr(a["uv"]),
+            ptr(a["max_err"]), ptr(a["hyp_off"]), ptr(a["draws"]), ptr(n_in), ptr(flags), ptr(R), ptr(t), ptr(first),
+            ptr(best), ptr(Tcw), ptr(n_ref)), "sqlm_pnp_ransac")
+        self.pnp_ransac_pairs = np.diff(a["pair_off"])
+        o = a["hyp_off"]
+        return [dict(n_inliers=n_in[o[k]:o[k + 1]], flags=flags[o[k]:o[k + 1]], R=R[o[k]:o[k + 1]],
+                     t=t[o[k]:o[k + 1]], first_return=int(first[k]), best=int(best[k]), Tcw=Tcw[k],
+                     n_refined=int(n_ref[k])) for k in range(P)]
+
+    def pnp_ransac_inliers(self, prob: int, hyp: int):
+        """mvbInliersi (N,) uint8 of hypothesis ``hyp`` of problem ``prob`` of the last pnp_ransac."""
+        n = int(self.pnp_ransac_pairs[prob])
+        mask = np.zeros(max(n, 1), np.uint8)
+        check(lib().sqlm_pnp_ransac_get_inliers(self._h, int(prob), int(hyp), ptr(mask)), "sqlm_pnp_ransac_get_inliers")
+        return mask[:n]
+
+    @staticmethod
+    def _pnp_diag():
+        return dict(ut=np.zeros((12, 12)), eig=np.zeros(12), betas=np.zeros((3, 4)), rep_err=np.zeros(3),
+                    chosen=np.zeros(1, np.int32))
+
+    def pnp_ransac_refined(self, prob: int, hyp: int):
+        """Refine() of the mask of the record-breaking hypothesis ``hyp``: a dict of R (3,3), t (3,), mask (N,)
+        uint8, n_inliers and the diagnostics of pnp_ransac_hypothesis. SqlmError (STATE) if ``hyp`` is no record."""
+        n = int(self.pnp_ransac_pairs[prob])
+        d = self._pnp_diag()
+        R, t, mask, cnt = np.zeros((3, 3)), np.zeros(3), np.zeros(max(n, 1), np.uint8), np.zeros(1, np.int32)
+        check(lib().sqlm_pnp_ransac_get_refined(self._h, int(prob), int(hyp), ptr(R), ptr(t), ptr(mask), ptr(cnt),
+                                                ptr(d["ut"]), ptr(d["eig"]), ptr(d["betas"]), ptr(d["rep_err"]),
+                                                ptr(d["chosen"])), "sqlm_pnp_ransac_get_refined")
+        d.update(R=R, t=t, mask=mask[:n], n_inliers=int(cnt[0]), chosen=int(d["chosen"][0]))
+        return d
+
+    def pnp_ransac_hypothesis(self, prob: int, hyp: int):
+        """Diagnostics of hypothesis ``hyp``: a dict of idx (4,), ut (12,12) rows by descending eigenvalue, eig
+        (12,), betas (3,4) after Gauss-Newton, rep_err (3,), chosen."""
+        d = self._pnp_diag()
+        idx = np.zeros(4, np.int32)
+        check(lib().sqlm_pnp_ransac_get_hypothesis(self._h, int(prob), int(hyp), ptr(idx), ptr(d["ut"]), ptr(d["eig"]),
+                                                   ptr(d["betas"]), ptr(d["rep_err"]), ptr(d["chosen"])),
+              "sqlm_pnp_ransac_get_hypothesis")
+        d.update(idx=idx, chosen=int(d["chosen"][0]))
+        return d
+
     # ------------------------------------------------------------- motion-only BA
     def _pose_out(self, a, P):
         n = int(a["obs_off"][-1])
