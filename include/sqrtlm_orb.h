@@ -9,7 +9,10 @@
  * (src/frontend/ORBmatcher.cc:573-718, :2096-2116). Frame::ExtractORB
  * (src/data_structure/Frame.cc) calls the extractor once per image; the
  * adapter replaces that call with sqlm_orb_extract and copies the arrays into
- * cv::KeyPoint / cv::Mat. The last section is the DBoW2
+ * cv::KeyPoint / cv::Mat. Two further sections: the map-point
+ * steps of LocalMapping (the match loop of CreateNewMapPoints and the MapPoint
+ * refresh, which consume the output of sqlm_orb_search_for_triangulation and
+ * sqlm_orb_fuse), and the DBoW2
  * vocabulary: ORBVocabulary::transform (Frame / KeyFrame::ComputeBoW) and
  * ORBVocabulary::score for a batch of keyframes.
  *
@@ -215,6 +218,95 @@ int sqlm_orb_search_for_triangulation(sqlm_ctx *ctx, const sqlm_bow_frame *K1, c
                                       const float *C1, const float *T2w, const float *cam2,
                                       const float *scale_factors2, int n_levels2, const float *F12, int only_stereo,
                                       int check_ori, int32_t *m12, int *n_matches);
+
+/* ---- LocalMapping: triangulation of new map points and the map-point refresh ----
+ *
+ * A keyframe as LocalMapping::CreateNewMapPoints reads it (src/backend/
+ * LocalMapping.cc:329-654): kps = mvKeysUn [n], uright = mvuRight (NULL:
+ * monocular), scale_factors = mvScaleFactors and level_sigma2 = mvLevelSigma2
+ * [n_levels], Tcw = the 3x4 rows of GetPose() (float, row-major), fx fy cx cy
+ * invfx invfy. */
+typedef struct sqlm_tri_frame {
+  const sqlm_keypoint *kps;
+  const float *uright;
+  const float *scale_factors;
+  const float *level_sigma2;
+  int32_t n, n_levels;
+  float Tcw[12];
+  float fx, fy, cx, cy, invfx, invfy;
+} sqlm_tri_frame;
+
+/* kf1 = mpCurrentKeyFrame, kf2 = the neighbour pKF2, ratio_factor =
+ * 1.5f * mpCurrentKeyFrame->mfScaleFactor (:364). */
+typedef struct sqlm_tri_pair {
+  sqlm_tri_frame kf1, kf2;
+  float ratio_factor;
+  int32_t pad;
+} sqlm_tri_pair;
+
+/* The match loop of CreateNewMapPoints (:436-624) for n_pair keyframe pairs in
+ * one launch (the reference's call is n_pair = 1 per neighbour; the per-pair
+ * pre-tests, baseline / ComputeSceneMedianDepth and ComputeF12, stay with the
+ * caller). Pair p owns the matches [match_off[p], match_off[p+1]) of matches
+ * [n_match][2] = vMatchedIndices (idx1, idx2); match_off[0] = 0.
+ *
+ * Per match: x3d [3] and reason: 0 a map point is created, 1 parallax test
+ * (:496), 2 x3D(3) == 0 (:511), 3 z1 <= 0, 4 z2 <= 0, 5 / 6 reprojection in
+ * keyframe 1 / 2, 7 a zero distance (:611), 8 scale consistency (:623). x3d is
+ * the triangulated point for reasons 0 and 3 to 8 and zero otherwise. n_new [n_pair] =
+ * the matches of reason 0 (nnew's share of the pair). The arithmetic is the
+ * reference's in its precisions and its order; cv::SVD::compute of the 4x4 A is
+ * a fixed-sweep one-sided Jacobi SVD in double. Every test after
+ * the parallax test is evaluated in its accepting form, so a NaN rejects.
+ *
+ * Checked on the host before the device is touched. SQLM_ERR_INVALID_ARG: a
+ * NULL array, offsets that do not ascend from 0, idx1 / idx2 outside the
+ * keyframes, an octave outside [0, n_levels). SQLM_ERR_UNSUPPORTED: a matched
+ * keypoint with uright >= 0 (the stereo branch, :476-524, is not provided).
+ * n_pair = 0 and pairs without matches are valid. */
+int sqlm_triangulate_pairs(sqlm_ctx *ctx, int n_pair, const sqlm_tri_pair *pairs, const int64_t *match_off,
+                           const int32_t *matches, float *x3d, uint8_t *reason, int32_t *n_new);
+/* The same text on the CPU, without a context. sweeps = the Jacobi sweep count
+ * (0: the library's). */
+int sqlm_triangulate_pairs_host(int n_pair, const sqlm_tri_pair *pairs, const int64_t *match_off,
+                                const int32_t *matches, int sweeps, float *x3d, uint8_t *reason, int32_t *n_new);
+/* Jacobi sweeps, lanes (matches) of a workgroup, lanes of a wavefront, 0 */
+int sqlm_triangulate_info(int32_t out[4]);
+
+/* MapPoint::ComputeDistinctiveDescriptors (src/data_structure/MapPoint.cc:
+ * 382-481) and UpdateNormalAndDepth (:531-578) for n_pt map points. Point j
+ * owns the observations [obs_off[j], obs_off[j+1]) in the caller's order
+ * (obs_off[0] = 0); either half is switched off by its NULL observation array.
+ *
+ * Descriptor half: obs_desc [n_obs][32] = the observing keyframes' descriptors
+ * in the order of :404-429. best_idx [n_pt] = the descriptor, as an index into
+ * the point's own list, whose median Hamming distance to all of the point's
+ * descriptors (its own 0 included; the element at index (size_t)(0.5 * (N - 1))
+ * of the ascending row) is least, the first of equals; best_median [n_pt] that
+ * median. A point without observations gives -1 and INT32_MAX: mDescriptor
+ * stays as it is.
+ *
+ * Normal and depth half: obs_center [n_obs][3] = GetCameraCenter() of the
+ * observing keyframes in the order of :556; pos = mWorldPos, ref_center =
+ * mpRefKF->GetCameraCenter(), level_scale = mpRefKF->mvScaleFactors[level] of
+ * the point's keypoint in mpRefKF (:567-568), max_scale = mpRefKF->
+ * mvScaleFactors[nLevels - 1]. normal [n_pt][3] = mNormalVector, max_dist /
+ * min_dist = mfMaxDistance / mfMinDistance. A point without observations gives
+ * zeros (the reference returns early); a camera centre equal to the point
+ * gives IEEE's NaN. */
+int sqlm_map_points_update(sqlm_ctx *ctx, int n_pt, const int64_t *obs_off, const uint8_t *obs_desc,
+                           const float *obs_center, const float *pos, const float *ref_center,
+                           const float *level_scale, const float *max_scale, int32_t *best_idx,
+                           int32_t *best_median, float *normal, float *max_dist, float *min_dist);
+int sqlm_map_points_update_host(int n_pt, const int64_t *obs_off, const uint8_t *obs_desc, const float *obs_center,
+                                const float *pos, const float *ref_center, const float *level_scale,
+                                const float *max_scale, int32_t *best_idx, int32_t *best_median, float *normal,
+                                float *max_dist, float *min_dist);
+/* The largest observation count whose descriptors the kernel keeps in LDS, and
+ * of the context's last sqlm_map_points_update (ctx may be NULL: zeros): the
+ * points that took the LDS path, the points that read global memory, the
+ * kernels launched. */
+int sqlm_map_points_update_info(const sqlm_ctx *ctx, int32_t out[4]);
 
 /* ---- DBoW2 vocabulary: BoW transform and batched L1 score ----
  *

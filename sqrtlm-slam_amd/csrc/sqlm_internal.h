@@ -771,4 +771,35 @@ void launch_bow_score(int nq, const int32_t *q_word, const double *q_value, int 
 struct BowSolver;
 void bow_destroy(BowSolver *s);
 
+// LocalMapping's map-point steps (sqlm_mappoint.cpp host, sqlm_mappoint.hip
+// kernels, mappoint_dev.h the arithmetic): k_triangulate, a lane per match of
+// CreateNewMapPoints; k_mp_descriptor, a wavefront per map point of
+// ComputeDistinctiveDescriptors; k_mp_normal, a lane per point of UpdateNormalAndDepth.
+struct TriPair;
+struct TriMatch;
+struct TriDev {  // device pointers of one sqlm_triangulate_pairs call
+  const TriPair *pair = nullptr;    // [n_pair]
+  const int64_t *first = nullptr;   // [n_pair + 1] a pair's first match among the concatenated matches
+  const TriMatch *match = nullptr;  // [n_match]
+  int32_t n_pair = 0;
+  int64_t n_match = 0;
+  float *x3d = nullptr;             // [n_match][3]
+  uint8_t *reason = nullptr;        // [n_match]
+};
+struct MpDev {  // device pointers of one sqlm_map_points_update call
+  int32_t n_pt = 0;
+  const int64_t *obs_off = nullptr;  // [n_pt + 1]
+  const uint32_t *desc = nullptr;    // [n_obs][8]
+  const float *center = nullptr;     // [n_obs][3]
+  const float *pos = nullptr, *ref_center = nullptr;        // [n_pt][3]
+  const float *level_scale = nullptr, *max_scale = nullptr; // [n_pt]
+  int32_t *best_idx = nullptr, *best_median = nullptr;      // [n_pt]
+  float *normal = nullptr, *max_dist = nullptr, *min_dist = nullptr;
+};
+void launch_triangulate(const TriDev &d, hipStream_t st);
+void launch_mp_descriptor(const MpDev &d, hipStream_t st);
+void launch_mp_normal(const MpDev &d, hipStream_t st);
+struct MapPointSolver;
+void mappoint_destroy(MapPointSolver *s);
+
 }  // namespace sqlm

@@ -69,7 +69,10 @@ ORB_EXPORTS = ["sqlm_orb_extract", "sqlm_orb_get_level", "sqlm_orb_match_bf", "s
                "sqlm_orb_search_by_sim3", "sqlm_orb_search_by_bow_kf_frame", "sqlm_orb_search_by_bow_kf_kf", "sqlm_orb_search_for_triangulation",
                "sqlm_orb_bench_extract",
                # DBoW2 vocabulary: BoW transform and batched L1 score
-               "sqlm_voc_create", "sqlm_voc_destroy", "sqlm_voc_info", "sqlm_bow_transform", "sqlm_bow_score"]
+               "sqlm_voc_create", "sqlm_voc_destroy", "sqlm_voc_info", "sqlm_bow_transform", "sqlm_bow_score",
+               # LocalMapping: triangulation of new map points and the map-point refresh
+               "sqlm_triangulate_pairs", "sqlm_triangulate_pairs_host", "sqlm_triangulate_info",
+               "sqlm_map_points_update", "sqlm_map_points_update_host", "sqlm_map_points_update_info"]
 
 
 class SqlmError(RuntimeError):
@@ -215,6 +218,17 @@ def lib() -> C.CDLL:
             # rep_err, chosen
             L.sqlm_pnp_ransac_hypothesis_host.argtypes = [C.c_int] + [P] * 16
             L.sqlm_pnp_ransac_refine_host.argtypes = [C.c_int] + [P] * 15
+        if hasattr(L, "sqlm_triangulate_pairs"):
+            P = C.c_void_p
+            # [ctx,] n_pair, pairs, match_off, matches, [sweeps,] x3d, reason, n_new
+            L.sqlm_triangulate_pairs.argtypes = [P, C.c_int] + [P] * 6
+            L.sqlm_triangulate_pairs_host.argtypes = [C.c_int, P, P, P, C.c_int, P, P, P]
+            L.sqlm_triangulate_info.argtypes = [P]
+            # [ctx,] n_pt, obs_off, obs_desc, obs_center, pos, ref_center, level_scale, max_scale, best_idx,
+            # best_median, normal, max_dist, min_dist
+            L.sqlm_map_points_update.argtypes = [P, C.c_int] + [P] * 12
+            L.sqlm_map_points_update_host.argtypes = [C.c_int] + [P] * 12
+            L.sqlm_map_points_update_info.argtypes = [P, P]
         _lib = L
     return _lib
 

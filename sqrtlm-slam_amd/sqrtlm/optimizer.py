@@ -434,6 +434,28 @@ class Context:
         d.update(idx=idx, chosen=int(d["chosen"][0]))
         return d
 
+    # ------------------------------------------------------------- LocalMapping's map points
+    def triangulate_pairs(self, pairs):
+        """sqlm_triangulate_pairs on a list of mappoint.TriPair: the match loop
+        of CreateNewMapPoints for every pair in one launch. Returns a dict of
+        x3d (n,3) float32, reason (n,) uint8, n_new (n_pair,) and the CSR
+        offsets ``off`` over the concatenated matches."""
+        from . import mappoint as _mp
+        return _mp.triangulate_pairs(self, pairs)
+
+    def map_points_update(self, batch):
+        """sqlm_map_points_update on a mappoint.MapPointBatch:
+        ComputeDistinctiveDescriptors and UpdateNormalAndDepth of every point.
+        Returns a dict of best_idx, best_median, normal, max_dist, min_dist
+        (the keys of a half that is switched off are absent)."""
+        from . import mappoint as _mp
+        return _mp.map_points_update(self, batch)
+
+    def map_points_update_info(self):
+        """dict(lds_max, n_lds, n_global, n_launch) of the last map_points_update."""
+        from . import mappoint as _mp
+        return _mp.map_points_update_info(self)
+
     # ------------------------------------------------------------- motion-only BA
     def _pose_out(self, a, P):
         n = int(a["obs_off"][-1])
