@@ -642,6 +642,10 @@ int sqlm_ctx_set_host_p2p(sqlm_ctx *ctx, sqlm_p2p_fn fn, void *user);
 int sqlm_bench_iterations(sqlm_ctx *ctx, int warmup, int n, double *ms_per_iter, double *kernel_ms,
                           sqlm_stats *stats);
 const char *sqlm_kernel_timer_name(int i);
+/* Diagnostic: the cyclic reduction this process launched last on the plain
+ * band solve: out[0] = index of the first superblock (1, or 0 with
+ * SQLM_CR_LO0=1), out[1] = elimination levels, out[2] = the top superblock. */
+int sqlm_debug_cr_levels(int out[3]);
 
 #ifdef __cplusplus
 }

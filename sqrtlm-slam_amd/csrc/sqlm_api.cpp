@@ -1047,6 +1047,12 @@ int sqlm_bench_iterations(sqlm_ctx *c, int warmup, int n, double *ms_per_iter, d
 int sqlm_debug_tile_profile(long long *out) { return sqlm::tile_profile_read(out); }
 #endif
 
+int sqlm_debug_cr_levels(int out[3]) {
+  if (!out) return SQLM_ERR_INVALID_ARG;
+  sqlm::cr_last_levels(out);
+  return SQLM_OK;
+}
+
 const char *sqlm_kernel_timer_name(int i) {
   return (i >= 0 && i < SQLM_NKERNEL_TIMERS) ? kTimerNames[i] : "";
 }

@@ -459,7 +459,7 @@ __device__ __forceinline__ void aug_body(aug::Shared &sh, const CRView &v, int h
   using namespace aug;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = v.n, nt = n >> 4;
-  const bool left = MODE == 0, right = MODE != 1 && I + h < v.p, first = sidx == 0;
+  const bool left = MODE == 0 && I - h >= v.lo, right = MODE != 1 && I + h < v.p + v.lo, first = sidx == 0;
   bool tmo = false;
   for (int t = threadIdx.x; t < 2 * kMaxNt + kPairs + 17; t += blockDim.x) {
     if (t < kMaxNt) sh.fT[t] = 0;

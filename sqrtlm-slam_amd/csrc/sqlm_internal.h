@@ -279,6 +279,10 @@ constexpr int kMaxFreePoses = 131072;
 struct CRPlan {
   bool enabled = false;
   int B = 0, p = 0, n = 0;
+  // Numbering of the superblocks inside the cyclic reduction: 1 = the first
+  // real superblock is index 1 (the plain band solve: floor(log2 p) levels),
+  // 0 = index 0 (band + border, and SQLM_CR_LO0=1: ceil(log2 p) levels)
+  int lo = 0;
   int nband = 0;                 // band cameras
   int R = 0, Rp = 0, nbc = 0;    // border width (16-padded, kCRMaxN-padded), border cameras
   std::vector<int> sched;        // concatenated lists (host); dev copy below
@@ -384,9 +388,11 @@ int launch_cr_solve(const DevProblem &d, const CRPlan &pl, hipStream_t st, bool 
 // band + border layout: clear F^T / the border system before S is assembled into it
 void launch_arrow_clear(const DevProblem &d, const CRPlan &pl, hipStream_t st);
 // CR levels + top + back substitution on blocks already in CR layout
-// (sync: every back-substitution level in one launch; null: one launch per level)
+// (sync: every back-substitution level in one launch; null: one launch per level;
+// lo: the superblock numbering, CRPlan::lo)
 void launch_cr_core(double *D, double *L, double *E, double *A, double *C, double *g, double *x, int *flags, int p, int n,
-                    hipStream_t st, CRSync *sync = nullptr);
+                    hipStream_t st, CRSync *sync = nullptr, int lo = 0);
+void cr_last_levels(int out[3]);  // lo, level count, top of the latest launch_cr_core (diagnostic)
 // Dense SPD solve (sqlm_rcs_solve.hip): A (n x n, lower, n % kCRMaxN == 0) is
 // factored in place into L (+ diagonal block inverses Linv), r is consumed,
 // x = A^-1 r; flags[0] is cleared on a non-positive pivot. band > 0: A is a

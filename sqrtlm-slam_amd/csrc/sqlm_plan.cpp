@@ -370,7 +370,10 @@ bool plan_rcs(int nP, const std::vector<int> &s_row, const std::vector<int> &s_c
   pl.p = (nband + B - 1) / B;
   pl.n = n;
   pl.nband = nband;
-  if (nbc == 0) return true;
+  if (nbc == 0) {
+    pl.lo = std::getenv("SQLM_CR_LO0") ? 0 : 1;  // read per plan: tests switch it
+    return true;
+  }
   pl.nbc = nbc;
   pl.R = (6 * nbc + 15) / 16 * 16;
   pl.Rp = (pl.R + kCRMaxN - 1) / kCRMaxN * kCRMaxN;

@@ -63,6 +63,43 @@ void pattern_from_tiles(int nP, const TileBuild &tb, std::vector<int> &s_row, st
 void build_tiles_finish(int nP, const std::vector<int> &s_row, const std::vector<int> &s_col, TilePlan &tp,
                         TileBuild &tb);
 int cr_superblock_width(int bmin, int nband);
+
+// Level arithmetic of the block cyclic reduction over p superblocks numbered
+// lo .. p + lo - 1 (CRPlan::lo): level l runs at stride h[l] = 2^l, eliminates
+// the n_odd[l] odd multiples of h[l] (I = h + 2 h q) and updates the n_even[l]
+// even ones (J = 2 h (q + lo)); levels run while two superblocks are alive and
+// `top` is the survivor. lo = 0: ceil(log2 p) levels, top 0. lo = 1:
+// floor(log2 p) levels, top the largest power of two <= p. The one-launch back
+// substitution holds back_grid workgroups, the levels coarsest first
+// (cr_back_block). launch_cr_core takes its grids from here and
+// tools/cr_levels_check.cpp checks them against a simulated elimination.
+struct CRLevels {
+  static constexpr int kMax = 32;
+  int lo = 0, top = 0, count = 0, back_grid = 0;
+  int h[kMax] = {}, n_odd[kMax] = {}, n_even[kMax] = {};
+};
+inline CRLevels cr_levels(int p, int lo) {
+  CRLevels L;
+  L.lo = lo;
+  const int last = p + lo - 1;  // highest superblock index
+  int h = 1;
+  for (; L.count < CRLevels::kMax && last / h + 1 - lo >= 2; h *= 2) {  // multiples of h in [lo, last]
+    L.h[L.count] = h;
+    L.n_odd[L.count] = (last + h) / (2 * h);
+    L.n_even[L.count] = last / (2 * h) + 1 - lo;
+    L.back_grid += L.n_odd[L.count];
+    ++L.count;
+  }
+  L.top = lo ? h : 0;
+  return L;
+}
+// Workgroup b of the one-launch back substitution -> (level, superblock I):
+// what k_cr_back_all computes from its block index.
+inline void cr_back_block(const CRLevels &L, int b, int &level, int &I) {
+  level = L.count - 1;
+  while (level > 0 && b >= L.n_odd[level]) b -= L.n_odd[level--];
+  I = L.h[level] + 2 * L.h[level] * b;
+}
 bool plan_rcs(int nP, const std::vector<int> &s_row, const std::vector<int> &s_col, CRPlan &pl,
               std::vector<int> &cam_pos);
 

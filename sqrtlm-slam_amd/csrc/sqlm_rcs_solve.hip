@@ -32,10 +32,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cstdlib>
 
 #include "sqlm_internal.h"
+#include "sqlm_plan.h"
 
 namespace sqlm {
 
@@ -354,6 +356,14 @@ struct CRView {
   int ld;     // k_cr_aug<1, *> only: nonzero = D is one block with this row stride (dense solve)
   int *done = nullptr;  // k_cr_back_all: done[I] == epoch once x_I is published
   int epoch = 0;
+  // The real superblocks are I = lo .. p + lo - 1 and every level eliminates
+  // the odd multiples of h among them. lo = 0: ceil(p / 2) survive a level and
+  // the last survivor is `top` = 0. lo = 1 (the plain band solve,
+  // launch_cr_core): floor(p / 2) survive -- one level fewer whenever p is not
+  // a power of two -- and `top` is the largest power of two <= p. With lo = 1
+  // every array pointer above is set one block before the storage, so
+  // superblock I is storage block I - 1 and nothing outside the solve changes.
+  int lo = 0, top = 0;
 };
 
 __device__ __forceinline__ double *blk(double *base, int I, int n) { return base + (size_t)I * n * n; }
@@ -649,8 +659,8 @@ inline int cr_split(int n_odd, int nt) { return std::max(1, std::min(2 * nt, 256
 __device__ __forceinline__ void cr_update_item(const CRView &v, int h, int lb) {
   const int n = v.n, nt = n >> 4, nd = nt * (nt + 1) / 2, items = nd + nt * nt + nt;
   const int ev = lb / items, rem = lb - ev * items;
-  const int J = 2 * h * ev;
-  const bool right = J + h < v.p, left = J >= h;
+  const int J = 2 * h * (ev + v.lo), pe = v.p + v.lo;
+  const bool right = J + h < pe, left = J - h >= v.lo;
   const int lane = threadIdx.x & 63, r16 = lane & 15, k4 = lane >> 4;
   if (rem < nd) {
     int ti = 0, tj = rem;
@@ -664,7 +674,7 @@ __device__ __forceinline__ void cr_update_item(const CRView &v, int h, int lb) {
     if (right || left) tile_store(blk(v.D, J, n), n, ti, tj, acc, -1.0, true);
   } else if (rem < nd + nt * nt) {
     const int t = rem - nd, ti = t / nt, tj = t - ti * nt;
-    if (right && J + 2 * h < v.p) {
+    if (right && J + 2 * h < pe) {
       const d4 acc = tile_gemm<true, false, false>(blk(v.A, J + h, n), blk(v.C, J + h, n), n, ti, tj);
       tile_store(blk(v.E, J, n), n, ti, tj, acc, -1.0, false);
     }
@@ -733,7 +743,7 @@ __device__ __forceinline__ void cr_back_body(const CRView &v, int h, int I, doub
   const int n = v.n;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lo = lane & 7, hi = lane >> 3;
   const bool act = wave < (n >> 4);
-  const bool right = I + h < v.p;
+  const bool right = I + h < v.p + v.lo, left = I - h >= v.lo;
   // 16-byte loads, eight lanes per 128-byte line; every global load is issued
   // before the first use (one memory round trip, 56 loads in flight).
   // y = z - A x_{I-h} - C x_{I+h}: lane (hi, lo) takes rows 16 wave + hi (+8),
@@ -743,19 +753,20 @@ __device__ __forceinline__ void cr_back_body(const CRView &v, int h, int I, doub
   using d2 = HIP_vector_type<double, 2>;
   const int ca = 2 * lo;
   const d2 *A = reinterpret_cast<const d2 *>(blk(v.A, I, n)), *C = reinterpret_cast<const d2 *>(blk(v.C, I, n));
-  const d2 *xl = reinterpret_cast<const d2 *>(v.x + (size_t)(I - h) * n);
+  const d2 *xl = reinterpret_cast<const d2 *>(v.x + (size_t)(I - (left ? h : 0)) * n);
   const d2 *xr = reinterpret_cast<const d2 *>(v.x + (size_t)(I + (right ? h : 0)) * n);
   const d2 *Li = reinterpret_cast<const d2 *>(blk(v.L, I, n));
   const int r0 = 16 * wave + hi, hn = n >> 1;
   d2 a0[kCRMaxN / 16], a1[kCRMaxN / 16], c0[kCRMaxN / 16], c1[kCRMaxN / 16], vl[kCRMaxN / 16], vr[kCRMaxN / 16];
   d2 li[kCRMaxN / 8];
   if (act) {
+  // no left neighbour: zero operands (A_I is not formed), the sums below unchanged
 #pragma unroll
   for (int u = 0; u < kCRMaxN / 16; ++u) {
     const int c = kclamp(16 * u + ca, n) >> 1;
-    a0[u] = A[r0 * hn + c];
-    a1[u] = A[(r0 + 8) * hn + c];
-    vl[u] = xl[c];
+    a0[u] = left ? A[r0 * hn + c] : d2(0.0, 0.0);
+    a1[u] = left ? A[(r0 + 8) * hn + c] : d2(0.0, 0.0);
+    vl[u] = left ? xl[c] : d2(0.0, 0.0);
   }
   if (LINV) {
 #pragma unroll
@@ -881,7 +892,7 @@ __device__ __forceinline__ void back_u_body(double *sm, const CRView &v, int h, 
 template <bool TOP>
 __global__ __launch_bounds__(512) void k_cr_back_u(CRView v, int h) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
-  back_u_body<TOP>(sm, v, h, TOP ? 0 : h + 2 * h * blockIdx.x);
+  back_u_body<TOP>(sm, v, h, TOP ? v.top : h + 2 * h * blockIdx.x);
 }
 
 // ---- every back-substitution level in one launch ----------------------------
@@ -890,10 +901,16 @@ __global__ __launch_bounds__(512) void k_cr_back_u(CRView v, int h) {
 // 4's band for ~2 us of arithmetic each). Here one launch holds a workgroup per
 // odd superblock of every level, coarsest level first: each loads its
 // operands (A_I, C_I, z_I, U_I, T), written by earlier launches, at once, then
-// waits for its neighbours' solutions x_{I-h}, x_{I+h} -- superblock 0 (the top
-// solve, an earlier launch) or superblocks of coarser levels, i.e. workgroups
-// with lower ids, dispatched before it, so the launch drains at any residency
-// -- and runs k_cr_back_u's arithmetic in the same order (the same bits).
+// waits for its neighbours' solutions x_{I-h}, x_{I+h} (those that exist:
+// lo <= I - h, I + h < p + lo) -- and runs k_cr_back_u's arithmetic in the same
+// order (the same bits). The launch drains at any residency, in either
+// numbering (CRView::lo): I is an odd multiple of h, so I - h and I + h are
+// multiples of 2h. A multiple of 2h survives level h, hence it is v.top (the
+// top solve, an earlier launch: no wait) or an odd multiple of a coarser
+// h' > h, whose workgroup has a lower id because the coarsest level comes
+// first. A waiting workgroup therefore only waits on lower-numbered
+// workgroups, dispatched before it (tools/cr_levels_check restates the map on
+// the host and checks this for every p).
 // Hand-off across the chip (per-XCD L2s): x_I is stored write-through (agent
 // scope, sc1), drained (vmcnt(0)) by every storing wave, then after a barrier
 // one lane stores done[I] = epoch (sc1; a per-solve counter, so nothing is
@@ -908,7 +925,7 @@ __global__ __launch_bounds__(512) void k_cr_back_u(CRView v, int h) {
 // aug::spin / spin_to, report a timeout after it has completed, so
 // tests/test_gpu_fail_loud.py runs this hand-off's give-up path too.
 __device__ __forceinline__ bool wait_x(const CRView &v, int J) {
-  bool ok = J == 0;  // the top superblock: solved by an earlier launch
+  bool ok = J == v.top;  // the top superblock: solved by an earlier launch
   const int *f = v.done + J;
   for (int it = 0; !ok && it < aug::kSpinLimit; ++it) {
     if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == v.epoch) ok = true;
@@ -930,7 +947,7 @@ __device__ __forceinline__ void back_all_body(double *sm, const CRView &v, int h
   const int n = v.n, nt = n >> 4;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, q = lane >> 4, r = lane & 15;
   const int lo = lane & 7, hi = lane >> 3;
-  const bool right = I + h < v.p;
+  const bool right = I + h < v.p + v.lo, left = I - h >= v.lo;
   if (threadIdx.x < aug::kMaxNt) fx[threadIdx.x] = 0;
   // this wave's U row and T_i (blockDim = 64 nt: wave i owns block row i)
   const int i = wave;
@@ -951,11 +968,12 @@ __device__ __forceinline__ void back_all_body(double *sm, const CRView &v, int h
   const d2 *A = reinterpret_cast<const d2 *>(blk(v.A, I, n)), *C = reinterpret_cast<const d2 *>(blk(v.C, I, n));
   const int r0 = 16 * wave + hi, hn = n >> 1;
   d2 a0[kCRMaxN / 16], a1[kCRMaxN / 16], c0[kCRMaxN / 16], c1[kCRMaxN / 16];
+  // no left neighbour: zero operands (A_I is not formed), the sums below unchanged
 #pragma unroll
   for (int uu = 0; uu < kCRMaxN / 16; ++uu) {
     const int c = kclamp(16 * uu + ca, n) >> 1;
-    a0[uu] = A[r0 * hn + c];
-    a1[uu] = A[(r0 + 8) * hn + c];
+    a0[uu] = left ? A[r0 * hn + c] : d2(0.0, 0.0);
+    a1[uu] = left ? A[(r0 + 8) * hn + c] : d2(0.0, 0.0);
   }
   if (right) {
 #pragma unroll
@@ -971,19 +989,20 @@ __device__ __forceinline__ void back_all_body(double *sm, const CRView &v, int h
   // L1 invalidate, ~1.7 us) is needed (MI355X_MICROARCH.md, hand-off table
   // row 1: one flag per storing workgroup, one workgroup per CU)
   if (threadIdx.x == 0) {
-    bool ok = wait_x(v, I - h);
+    bool ok = true;
+    if (left) ok = wait_x(v, I - h);
     if (right) ok = wait_x(v, I + h) && ok;
     tmo_s = ok ? 0 : 1;
   }
   __syncthreads();
   const bool tmo = tmo_s != 0;
-  const double *xl = v.x + (size_t)(I - h) * n, *xr = v.x + (size_t)(I + (right ? h : 0)) * n;
+  const double *xl = v.x + (size_t)(I - (left ? h : 0)) * n, *xr = v.x + (size_t)(I + (right ? h : 0)) * n;
   d2 vl[kCRMaxN / 16], vr[kCRMaxN / 16];
 #pragma unroll
   for (int uu = 0; uu < kCRMaxN / 16; ++uu) {
     const int c = (kclamp(16 * uu + ca, n) >> 1) << 1;  // the pair cr_back_body's 16-byte load takes
-    vl[uu].x = ld_x(xl + c);
-    vl[uu].y = ld_x(xl + c + 1);
+    vl[uu].x = left ? ld_x(xl + c) : 0.0;
+    vl[uu].y = left ? ld_x(xl + c + 1) : 0.0;
     if (right) {
       vr[uu].x = ld_x(xr + c);
       vr[uu].y = ld_x(xr + c + 1);
@@ -1049,7 +1068,7 @@ __global__ __launch_bounds__(512) void k_cr_back_all(CRView v, int h_top) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   int b = blockIdx.x, h = h_top;
   for (;;) {
-    const int n_odd = (v.p - h + 2 * h - 1) / (2 * h);
+    const int n_odd = (v.p + v.lo - 1 + h) / (2 * h);  // odd multiples of h in [lo, p + lo)
     if (b < n_odd || h == 1) break;
     b -= n_odd;
     h >>= 1;
@@ -1500,7 +1519,7 @@ __device__ __forceinline__ void trsm_strip(const CRView &v, int h, int I, int s)
   const int n = v.n, nt = n >> 4, lane = threadIdx.x & 63, b = lane >> 4, i16 = lane & 15;
   const bool et = s < nt;
   const int J = et ? s : s - nt;
-  if (!et && I + h >= v.p) return;
+  if (et ? I - h < v.lo : I + h >= v.p + v.lo) return;  // no such neighbour
   const double *Lb = blk(v.L, I, n);
   d4 t[aug::kMaxNt];
 #pragma unroll
@@ -1873,42 +1892,59 @@ static void launch_arrow_solve(const DevProblem &d, const CRPlan &pl, hipStream_
   }
 }
 
+// numbering, level count and top of this process's latest launch_cr_core
+// (sqlm_debug_cr_levels: tests show which numbering a run really took)
+static std::atomic<int> g_cr_last[3];
+void cr_last_levels(int out[3]) {
+  for (int i = 0; i < 3; ++i) out[i] = g_cr_last[i].load();
+}
+
 // Levels, top solve and back substitution on D/E/g already in CR layout.
 void launch_cr_core(double *D, double *L, double *E, double *A, double *C, double *g, double *x, int *flags, int p,
-                    int n, hipStream_t st, CRSync *sync) {
-  CRView v{p, n, 0, 0, D, E, A, C, g, x, flags, L};
+                    int n, hipStream_t st, CRSync *sync, int lo) {
+  if (cr_legacy()) lo = 0;  // the round-2 kernels know superblock 0 as the top only
+  const CRLevels lv = cr_levels(p, lo);
+  g_cr_last[0] = lo;
+  g_cr_last[1] = lv.count;
+  g_cr_last[2] = lv.top;
+  // Superblock I of the view is storage block I - lo (CRView::lo). With lo = 1
+  // the view's block 0 lies before the storage and is never touched: every
+  // blk(v.*, I - h), v.g / v.x / v.done + (I - h) below sits behind a `left`
+  // guard (I - h >= v.lo), as every I + h sits behind `right`. A new kernel
+  // that reads a neighbour must carry both.
+  const size_t nn = (size_t)n * n;
+  CRView v{p, n, 0, 0, D - lo * nn, E - lo * nn, A - lo * nn, C - lo * nn, g - lo * n, x - lo * n, flags, L - lo * nn};
+  v.lo = lo;
+  v.top = lv.top;
   const size_t lds = cr_factor_lds(n);
   const int nt = n / 16, per = nt * nt, upd = nt * (nt + 1) / 2 + per + nt;
-  int h = 1;
-  for (; h < p; h *= 2) {
-    const int n_odd = (p - h + 2 * h - 1) / (2 * h);
-    const int n_even = (p + 2 * h - 1) / (2 * h);
-    launch_cr_level(v, h, n_odd, false, st);
+  for (int l = 0; l < lv.count; ++l) {
+    const int h = lv.h[l];
+    launch_cr_level(v, h, lv.n_odd[l], false, st);
     // (two waves per workgroup, a D tile's A^T A and C^T C at once: solve
     // 0.458 -> 0.473 ms, profiles/r05/ab_upd_half_lanes_cr_upd2w.log)
-    hipLaunchKernelGGL(k_cr_update_gemm, dim3(xcd_grid(n_even * upd)), dim3(64), 0, st, v, h, n_even * upd);
+    hipLaunchKernelGGL(k_cr_update_gemm, dim3(xcd_grid(lv.n_even[l] * upd)), dim3(64), 0, st, v, h, lv.n_even[l] * upd);
   }
   const size_t back_lds = 3 * kCRMaxN * sizeof(double) + aug::kMaxNt * sizeof(int);
   if (cr_legacy())
     hipLaunchKernelGGL(k_cr_top, dim3(1), dim3(512), lds, st, v);
-  else  // x_0 = U_0^-1 z_0 by the top factor's workgroup
-    hipLaunchKernelGGL((k_cr_aug<1, false, true>), dim3(1), dim3(aug::kThreads), sizeof(aug::Shared), st, v, 0, 0, 0, 1);
-  if (!cr_legacy() && p > 1 && sync && sync->done && sync->cap >= p) {  // every back level in one launch
+  else  // x_top = U_top^-1 z_top by the top factor's workgroup
+    hipLaunchKernelGGL((k_cr_aug<1, false, true>), dim3(1), dim3(aug::kThreads), sizeof(aug::Shared), st, v, 0, v.top, 0, 1);
+  if (!cr_legacy() && lv.count > 0 && sync && sync->done && sync->cap >= p) {  // every back level in one launch
     if (sync->epoch == INT_MAX) {  // (never in practice) restart the completion words
       (void)hipMemsetAsync(sync->done, 0, (size_t)sync->cap * sizeof(int), st);
       sync->epoch = 0;
     }
-    v.done = sync->done;
+    v.done = sync->done - lo;
     v.epoch = ++sync->epoch;
-    hipLaunchKernelGGL(k_cr_back_all, dim3(p - 1), dim3(64 * nt), back_lds, st, v, h / 2);
+    hipLaunchKernelGGL(k_cr_back_all, dim3(lv.back_grid), dim3(64 * nt), back_lds, st, v, lv.h[lv.count - 1]);
     return;
   }
-  for (h /= 2; h >= 1; h /= 2) {
-    const int n_odd = (p - h + 2 * h - 1) / (2 * h);
+  for (int l = lv.count - 1; l >= 0; --l) {
     if (cr_legacy())
-      hipLaunchKernelGGL(k_cr_back, dim3(n_odd), dim3(64 * nt), (size_t)n * sizeof(double), st, v, h);
+      hipLaunchKernelGGL(k_cr_back, dim3(lv.n_odd[l]), dim3(64 * nt), (size_t)n * sizeof(double), st, v, lv.h[l]);
     else
-      hipLaunchKernelGGL(k_cr_back_u<false>, dim3(n_odd), dim3(64 * nt), back_lds, st, v, h);
+      hipLaunchKernelGGL(k_cr_back_u<false>, dim3(lv.n_odd[l]), dim3(64 * nt), back_lds, st, v, lv.h[l]);
   }
 }
 
@@ -1922,7 +1958,7 @@ int launch_cr_solve(const DevProblem &d, const CRPlan &pl, hipStream_t st, bool 
     hipLaunchKernelGGL(k_cr_scatter, dim3(d.nP), dim3(64), 0, st, d, v);
   }
   if (pl.R) launch_arrow_solve(d, pl, st);
-  else launch_cr_core(d.cr_D, d.cr_L, d.cr_E, d.cr_A, d.cr_C, d.cr_g, d.cr_x, d.flags, pl.p, pl.n, st, sync);
+  else launch_cr_core(d.cr_D, d.cr_L, d.cr_E, d.cr_A, d.cr_C, d.cr_g, d.cr_x, d.flags, pl.p, pl.n, st, sync, pl.lo);
   if (gather) hipLaunchKernelGGL(k_cr_gather, dim3((6 * d.nP + 255) / 256), dim3(256), 0, st, d, v);
   return 0;
 }

@@ -30,7 +30,7 @@ EXPORTS = [
     "sqlm_comm_id_size", "sqlm_comm_get_unique_id", "sqlm_ctx_set_comm", "sqlm_ctx_set_host_comm",
     "sqlm_ctx_set_host_p2p", "sqlm_ctx_set_comm_selfloop", "sqlm_comm_selftest", "sqlm_ctx_comm_info",
     "sqlm_bench_iterations",
-    "sqlm_kernel_timer_name", "sqlm_set_stereo",
+    "sqlm_kernel_timer_name", "sqlm_debug_cr_levels", "sqlm_set_stereo",
     "sqlm_eg_set_problem", "sqlm_eg_optimize", "sqlm_eg_get_poses", "sqlm_eg_get_edge_chi2",
     "sqlm_eg_get_jacobians", "sqlm_eg_get_last_step", "sqlm_eg_get_exec_info",
     "sqlm_get_rcs_layout", "sqlm_get_exec_info", "sqlm_get_last_step",

@@ -159,6 +159,8 @@ int main(int argc, char **argv) {
   CK(hipMemset(dDone, 0, (size_t)p * sizeof(int)));
   sqlm::CRSync sync{dDone, p, 0};
   sqlm::CRSync *psync = std::getenv("CRB_LEVELS") ? nullptr : &sync;
+  // the numbering of the plain band solve (CRPlan::lo); SQLM_CR_LO0=1: the first superblock at index 0
+  const int lo = std::getenv("SQLM_CR_LO0") ? 0 : 1;
   double best = 1e30, sum = 0.0;
   for (int it = 0; it < reps + 2; ++it) {  // 2 warmups
     CK(hipMemcpyAsync(dD, D.data(), nb * 8, hipMemcpyHostToDevice, st));
@@ -167,7 +169,7 @@ int main(int argc, char **argv) {
     CK(hipMemcpyAsync(dflags, one, 16, hipMemcpyHostToDevice, st));
     CK(hipEventRecord(e0, st));
     if (std::getenv("CRB_VERBOSE")) std::fprintf(stderr, "launch %d ...\n", it);
-    sqlm::launch_cr_core(dD, dL, dE, dA, dC, dg, dx, dflags, p, n, st, psync);
+    sqlm::launch_cr_core(dD, dL, dE, dA, dC, dg, dx, dflags, p, n, st, psync, lo);
     CK(hipEventRecord(e1, st));
     CK(hipStreamSynchronize(st));
     CK(hipGetLastError());
