@@ -512,6 +512,150 @@ int sqlm_set_lidar_from_cloud_sets(sqlm_ctx *ctx, int32_t pose_index, int n_sets
  * any association. */
 int sqlm_lidar_get_exec_info(sqlm_ctx *ctx, int out[8]);
 
+/* LiDAR flat-feature extraction: the flat-point path of Frame::lidarProcess (Frame.cc:1243;
+ * CalculateRingAndTime :473, PointToImage :548, PrepareRing_flat :704, PrepareSubregion_flat
+ * :797, ExtractFeaturePoints :834 with using_flat_point = 1, using_sharp_point = 0) and the
+ * final transform of the clouds (:461-466), for a batch of sweeps. What a sweep yields depends
+ * on that sweep and the parameters alone. All arithmetic is IEEE, no FMA, in the precision and
+ * order the reference writes it (C++'s usual conversions); the reference's float atan / atan2 /
+ * sqrt calls are f(x) = (float)F((double)x) with F = sqlm_libm.h's atan / atan2 /
+ * the IEEE sqrt. Whether that equals glibc's atanf / atan2f on every input is unpinned (the
+ * reference cannot be built against); sqrt is exact either way. PI is M_PI.
+ *
+ * Per point i of a sweep (x, y, z float):
+ *   dropped when a coordinate is not finite (removeNaNFromPointCloud);
+ *   s = sqrtf(x x + y y), ang = (float)((double)(atanf(z / s) * 180.0f) / PI);
+ *   ring = ang >= -8.83 ? int((double)(2.0f - ang) * 3.0 + 0.5)
+ *                       : 32 + int((-8.83 - (double)ang) * 2.0 + 0.5);
+ *   dropped when ang is NaN (x = y = z = 0; the reference's conversion is undefined) or ring is
+ *   outside [0, 63]. The other points are the kept points, in input order.
+ *   azi = -atan2f(y, x).
+ * Per sweep: first / last = the first and last kept point;
+ *   startOri = (float)((double)azi[first] + PI), endOri = (float)((double)azi[last] + 3.0 PI),
+ *   then endOri = (float)(endOri - 2 PI) when endOri - startOri (float) > 3 PI, else
+ *   (float)(endOri + 2 PI) when it is < PI.
+ *   For a kept point, A(i) is the reference's not-yet-passed branch (:568-572): a = azi;
+ *   a < startOri - PI/2 -> a = (float)(a + 2 PI); else a > startOri + PI 3/2 -> a = (float)(a - 2 PI).
+ *   half = the lowest kept i with A(i) - startOri (float) > PI. A kept point i <= half uses
+ *   a = A(i); a later one the passed branch (:577-582) against endOri. halfPassed is thus a
+ *   minimum over indices, not a loop state.
+ *   col = (int((double)(a - startOri) / (2 PI) * col_num) + col_num) % col_num, row = ring;
+ *   a point with row >= row_num or col outside [0, col_num) claims no cell.
+ * Range image: a cell's occupant is the claiming point of least d = sqrtf((x x + y y) + z z),
+ *   the lowest input index among equal d (:617 is strict). A row's scan order is arrival order:
+ *   the cell's index is the rank, among the row's occupied cells, of the lowest input index
+ *   that claims the cell; the scan point at that index is the cell's occupant.
+ * A row (ring) r with n scan points is processed when ring_enabled[r] and
+ *   n - 1 > 2 max(num_curvature_regions_flat, num_curvature_regions_corner) (:846-854). With
+ *   c = num_curvature_regions_flat, the mask is the OR over i in [c, n - c) of the range each i
+ *   writes (:714-736): [i - c, i] or [i + 1, i + c]. Subregion j = 0 .. num_scan_subregions - 1
+ *   is [sp, ep] as :1053-1056, skipped when ep <= sp. Inside one, the curvature of scan point i
+ *   is :808-826 in float, the sums in j order; a neighbourhood int(25.0 / d + 0.5) + 1 that is
+ *   NaN or not below 2^30 takes the fallback like any that does not fit the scan. The
+ *   subregion's candidates are ordered by (curvature bits, index): non-negative floats order as
+ *   their bits, so this is std::sort's order of the pairs and independent of the algorithm.
+ * A candidate in that order is rejected as masked, then when not (double)curv < surf_curv_th;
+ *   else cw = int((double)d 0.01 / (deg_diff / 180.0 PI (double)d) + 0.5) (0 when NaN, at most
+ *   8), the search points are gathered in the order of :1088-1138 (the gather does not wrap
+ *   around the columns), fewer than 5 reject; the near points are those with
+ *   (double)CalcSquaredDiff < max_sq_dis, in gather order, at most 3 (2 cw + 1) = 51.
+ * Plane fit: the least-squares solution of A n = -1 (rows = near points, widened) by a
+ *   column-pivoted Householder QR in double with this fixed order. For k = 0, 1, 2: the squared
+ *   norm of every remaining column over rows k.. (summed in row order) is taken, the largest
+ *   becomes column k (the first of equals); when it is not above 1e-24 times the largest initial
+ *   squared column norm the fit is degenerate. beta = -sign(a_kk) sqrt(norm2) (sign(0) = +),
+ *   v = column / (a_kk - beta) below the diagonal, tau = (beta - a_kk) / beta; every later
+ *   column and the right side get w = tau (a_k + sum_s v_s a_s), a_k -= w, a_s -= v_s w in row
+ *   order. Back substitution x2 = c2 / r22, x1 = (c1 - r12 x2) / r11,
+ *   x0 = ((c0 - r01 x1) - r02 x2) / r00, unpermuted. Fewer than 3 near points are degenerate
+ *   too. Eigen's colPivHouseholderQr is not restated: it differs in rounding, and on a
+ *   rank-deficient neighbourhood it returns a minimum-norm-like answer where this rejects.
+ *   nrm = sqrt((x0 x0 + x1 x1) + x2 x2), d0 = 1 / nrm, n = x / nrm; the plane is invalid when
+ *   fabs(((n0 X + n1 Y) + n2 Z) + d0) > 0.1 for a near point (:1196-1205). The normal is
+ *   (float)n.
+ * Pick: the valid candidates of a subregion in sorted order; the first max_surf_less_flat are
+ *   less-flat points and the first max_surf_flat of those are flat points too. The reference's
+ *   break only stops early: every candidate after the one that fills the less-flat cap (with
+ *   a cap of 0: the first valid candidate and every later one) has reason OVER_CAP whatever
+ *   its own evaluation would give.
+ * Output order is the reference's push order: ring, subregion, sorted rank. Every output
+ *   point p and every normal n, as a point, translation included (:465-466 do that), goes
+ *   through `extrinsic` as sqlm_lidar_associate defines pcl::transformPointCloud:
+ *   (float)(((m0 x + m1 y) + m2 z) + m3) in double per coordinate. NULL is the identity and
+ *   copies the floats.
+ * A sweep without a kept point gives empty outputs (the reference would read points[0]).
+ * Coordinates whose squares overflow a float are undefined; no memory is touched out of bounds.
+ *
+ * Limits: row_num in [1, 128], col_num in [1, 4096], the neighbourhood half-width
+ * int(0.01 / (deg_diff / 180 PI) + 0.5) + 1 <= 8, using_sharp_point = 0 (the corner branch,
+ * :861-1038, is a sequential region growing and is not built): beyond them
+ * SQLM_ERR_UNSUPPORTED, before the device is touched. num_scan_subregions < 1,
+ * num_curvature_regions_flat < 1, a negative corner width or cap, deg_diff <= 0 and a sweep
+ * of 2^31 points or more are SQLM_ERR_INVALID_ARG. */
+#define SQLM_LF_MAX_ROWS 128
+#define SQLM_LF_MAX_COLS 4096
+#define SQLM_LF_MAX_HALF_WIDTH 8
+#define SQLM_LF_NONE 0      /* no candidate: the scan point lies in no processed subregion */
+#define SQLM_LF_MASKED 1
+#define SQLM_LF_CURVATURE 2
+#define SQLM_LF_FEW_SEARCH 3 /* fewer than 5 search points */
+#define SQLM_LF_DEGENERATE 4 /* fewer than 3 near points or a pivot below the tolerance */
+#define SQLM_LF_PLANE_INVALID 5
+#define SQLM_LF_OVER_CAP 6
+#define SQLM_LF_PICKED 7
+typedef struct sqlm_lidar_feat_params {
+  int32_t row_num, col_num;
+  int32_t num_scan_subregions;
+  int32_t num_curvature_regions_flat, num_curvature_regions_corner;
+  int32_t max_surf_flat, max_surf_less_flat;
+  int32_t using_sharp_point;
+  double surf_curv_th, max_sq_dis, deg_diff;
+  uint8_t ring_enabled[SQLM_LF_MAX_ROWS]; /* ring r (0-based) takes part in :1041-1045 */
+} sqlm_lidar_feat_params;
+
+/* The intermediate state of a call (tests and tools). Caller-allocated; any pointer may be
+ * NULL. n = sweep_off[n_sweep], S = n_sweep row_num. Scan points are numbered sweep by sweep,
+ * row by row, in scan order: row (s, r) owns [scan_off[s row_num + r], scan_off[.. + 1]). */
+typedef struct sqlm_lidar_feat_state {
+  int32_t *ring;        /* [n] ring of every input point, -1 for a dropped point */
+  int64_t *scan_off;    /* [S + 1] */
+  int32_t *scan_src;    /* [n] (first scan_off[S] used) the occupant's index within its sweep */
+  int32_t *scan_col;    /* [n] its column; its row is the scan's */
+  int32_t *image_index; /* [S][col_num] the cell's index within its row's scan, -1 = unoccupied */
+  uint8_t *mask;        /* [n] the ring mask, 0 on a row that is not processed */
+  float *curvature;     /* [n] 0 outside the processed subregions */
+  int32_t *neighbours;  /* [n] the curvature half-width used, 0 outside */
+  int32_t *sorted;      /* [n] at position row start + sp + k: the in-scan index of the subregion's rank k; -1 outside */
+  uint8_t *reason;      /* [n] SQLM_LF_* of every scan point */
+} sqlm_lidar_feat_state;
+
+/* Outputs are packed sweep after sweep: sweep s owns [flat_off[s], flat_off[s + 1]) of the
+ * flat arrays and likewise for less-flat; every array has room for n entries. */
+int sqlm_lidar_features(sqlm_ctx *ctx, int n_sweep, const int64_t *sweep_off /*[n_sweep+1]*/,
+    const float *xyz /*[n][3]*/, const sqlm_lidar_feat_params *params,
+    const double *extrinsic /*[16] row-major, NULL = identity*/,
+    int64_t *flat_off /*[n_sweep+1]*/, float *flat_xyz /*[n][3]*/, float *flat_normal /*[n][3]*/,
+    int64_t *less_off /*[n_sweep+1]*/, float *less_xyz /*[n][3]*/, float *less_normal /*[n][3]*/,
+    int32_t *less_row_col /*[n][2]*/);
+/* The same text compiled for the CPU; no context, no device. `state` may be NULL. */
+int sqlm_lidar_features_host(int n_sweep, const int64_t *sweep_off, const float *xyz,
+    const sqlm_lidar_feat_params *params, const double *extrinsic,
+    int64_t *flat_off, float *flat_xyz, float *flat_normal,
+    int64_t *less_off, float *less_xyz, float *less_normal, int32_t *less_row_col,
+    sqlm_lidar_feat_state *state);
+/* The state of the context's last sqlm_lidar_features, read back from the device; the arrays
+ * are sized by that call's arguments. SQLM_ERR_STATE before any call. */
+int sqlm_lidar_features_get_state(sqlm_ctx *ctx, sqlm_lidar_feat_state *state);
+/* out[0] = SQLM_LF_MAX_ROWS, out[1] = SQLM_LF_MAX_COLS, out[2] = kernel launches of the last
+ * call (0: nothing reached the device), out[3] = the largest subregion, out[4] = candidates
+ * (scan points in processed subregions), out[5] = candidates evaluated before the caps stopped
+ * their subregions (in steps of 64 per subregion), out[6] = less-flat points picked,
+ * out[7] = SQLM_LF_MAX_HALF_WIDTH. ctx may be NULL (the limits alone). */
+int sqlm_lidar_features_info(const sqlm_ctx *ctx, int32_t out[8]);
+/* Test probe of sqlm_libm.h's atan / atan2 as this library compiled them: out[i] =
+ * atan2 of (y[i], x[i]), or atan of y[i] where x is NULL. */
+int sqlm_lidar_feat_trig_probe(int64_t n, const double *y, const double *x, double *out);
+
 /* Results (write-back inputs, g2oOptimizer.cc:1167-1189, :306-360). */
 int sqlm_get_poses(sqlm_ctx *ctx, double *pose_q, double *pose_t);
 int sqlm_get_points(sqlm_ctx *ctx, double *pt);

@@ -152,6 +152,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   if (c->orb) orb_destroy(c->orb);
   if (c->bow) bow_destroy(c->bow);
   if (c->mappoint) mappoint_destroy(c->mappoint);
+  if (c->lidar_feat) lidar_feat_destroy(c->lidar_feat);
   for (auto &b : c->bufs)
     if (b.p) (void)hipFree(b.p);
   for (auto &b : c->pins) free_pinned(b);

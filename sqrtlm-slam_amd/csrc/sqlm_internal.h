@@ -808,4 +808,9 @@ void launch_mp_normal(const MpDev &d, hipStream_t st);
 struct MapPointSolver;
 void mappoint_destroy(MapPointSolver *s);
 
+// LiDAR flat-feature extraction (sqlm_lidar_feat.cpp host, sqlm_lidar_feat.hip kernels,
+// lidar_feat_dev.h the arithmetic and the launch interface)
+struct LidarFeatSolver;
+void lidar_feat_destroy(LidarFeatSolver *s);
+
 }  // namespace sqlm

@@ -58,6 +58,9 @@ EXPORTS = [
     "sqlm_pnp_ransac", "sqlm_pnp_ransac_get_inliers", "sqlm_pnp_ransac_get_refined", "sqlm_pnp_ransac_get_hypothesis",
     "sqlm_pnp_ransac_max_its", "sqlm_pnp_ransac_scan", "sqlm_pnp_ransac_hypothesis_host",
     "sqlm_pnp_ransac_refine_host",
+    # LiDAR flat-feature extraction (Frame::lidarProcess, flat-point path) and its host twin
+    "sqlm_lidar_features", "sqlm_lidar_features_host", "sqlm_lidar_features_get_state", "sqlm_lidar_features_info",
+    "sqlm_lidar_feat_trig_probe",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -218,6 +221,13 @@ def lib() -> C.CDLL:
             # rep_err, chosen
             L.sqlm_pnp_ransac_hypothesis_host.argtypes = [C.c_int] + [P] * 16
             L.sqlm_pnp_ransac_refine_host.argtypes = [C.c_int] + [P] * 15
+        if hasattr(L, "sqlm_lidar_features"):
+            P = C.c_void_p
+            L.sqlm_lidar_features.argtypes = [P, C.c_int] + [P] * 11
+            L.sqlm_lidar_features_host.argtypes = [C.c_int] + [P] * 12
+            L.sqlm_lidar_features_get_state.argtypes = [P, P]
+            L.sqlm_lidar_features_info.argtypes = [P, P]
+            L.sqlm_lidar_feat_trig_probe.argtypes = [C.c_int64, P, P, P]
         if hasattr(L, "sqlm_triangulate_pairs"):
             P = C.c_void_p
             # [ctx,] n_pair, pairs, match_off, matches, [sweeps,] x3d, reason, n_new
@@ -231,6 +241,24 @@ def lib() -> C.CDLL:
             L.sqlm_map_points_update_info.argtypes = [P, P]
         _lib = L
     return _lib
+
+
+LF_MAX_ROWS = 128
+
+
+class LidarFeatParams(C.Structure):
+    """sqlm_lidar_feat_params."""
+    _fields_ = [("row_num", C.c_int32), ("col_num", C.c_int32), ("num_scan_subregions", C.c_int32),
+                ("num_curvature_regions_flat", C.c_int32), ("num_curvature_regions_corner", C.c_int32),
+                ("max_surf_flat", C.c_int32), ("max_surf_less_flat", C.c_int32), ("using_sharp_point", C.c_int32),
+                ("surf_curv_th", C.c_double), ("max_sq_dis", C.c_double), ("deg_diff", C.c_double),
+                ("ring_enabled", C.c_uint8 * LF_MAX_ROWS)]
+
+
+class LidarFeatState(C.Structure):
+    """sqlm_lidar_feat_state: caller-allocated arrays, any may be NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("ring", "scan_off", "scan_src", "scan_col", "image_index", "mask",
+                                          "curvature", "neighbours", "sorted", "reason")]
 
 
 def check(status: int, what: str) -> None:
