@@ -656,6 +656,109 @@ int sqlm_lidar_features_info(const sqlm_ctx *ctx, int32_t out[8]);
  * atan2 of (y[i], x[i]), or atan of y[i] where x is NULL. */
 int sqlm_lidar_feat_trig_probe(int64_t n, const double *y, const double *x, double *out);
 
+/* ---- LiDAR depth image and keypoint depth association of a fusion frame ----
+ * The other LiDAR half of the reference's Frame constructor
+ * (src/data_structure/Frame.cc:290-313 and :333-408; line numbers below are that file's): the
+ * sweep is projected into the double depth image Depthimg_, and every ORB keypoint gets a
+ * class_id and an mvDepth from an 8 x 14 pixel patch of that image. A batch of frames shares
+ * rows, cols, the 3x4 `intrinsic` and the 4x4 `extrinsic` (double, row-major); frame f owns
+ * the points [sweep_off[f], sweep_off[f+1]) of xyz and the keypoints [key_off[f], key_off[f+1])
+ * of key_xy (mvKeys[i].pt, the distorted coordinates). The reference's loops overwrite, break
+ * and sort; each is restated as a rule that does not depend on an order of evaluation, and
+ * the arithmetic is IEEE in the order written here, nothing contracted into an FMA.
+ *
+ * Projection (:293-313). M = intrinsic extrinsic is formed once on the host,
+ *   M[r][c] = ((a0 b0 + a1 b1) + a2 b2) + a3 b3 (a = row r of intrinsic, b = column c of
+ *   extrinsic). Per point, (x, y, z) widened to double: zu, zv, zw = rows 0, 1, 2 of M applied
+ *   to (x, y, z, 1) and depth = row 2 of extrinsic applied to it, each
+ *   ((m0 x + m1 y) + m2 z) + m3, as sqlm_lidar_associate defines pcl::transformPointCloud.
+ *   How Eigen groups or fuses intrinsicMatrix*extrinsicMatrix*P_lidar is unpinned (the
+ *   reference cannot be built against).
+ *   u = int(zu / zw), v = int(zv / zw), truncating toward zero: a quotient in (-1, 0) lands
+ *   on 0. The point writes pixel (v, u) iff x, y, z are finite, x > SQLM_LD_MIN_X (:295 and
+ *   :308 together: x == 1 passes the first test and fails the second), and the quotients qu,
+ *   qv satisfy -1 < qu < cols and -1 < qv < rows, which is 0 <= u <= cols - 1 and
+ *   0 <= v <= rows - 1 for every quotient that converts to int32 and false for NaN, the
+ *   infinities and everything beyond int32 (the reference's int() of those is undefined; on
+ *   x86-64 it gives INT_MIN, which fails its bound test, so dropping them gives the same
+ *   image). A point with zw < 0 whose quotients land inside writes its negative depth, as
+ *   the reference does. A point with a non-finite coordinate is dropped (the reference's
+ *   cloud has been through removeNaNFromPointCloud by then, or would convert a NaN).
+ * Image. A pixel's occupant is the writing point of greatest input index (the loop
+ *   overwrites), its value that point's depth; unwritten pixels hold 0.0. n_written counts
+ *   writing points (depthpixel_num, :310), n_occupied distinct written pixels.
+ * min_v (:341-353) = the lowest row holding a pixel > 0.0 (as double), 0 when there is none:
+ *   a negative depth does not count, a depth in (0, 1) does.
+ * The patch's "seen" test (:366-367) reads the double into a uchar. With
+ *   t = (int32)trunc(depth) when |depth| < 2^31, else INT_MIN, a cell is seen iff
+ *   (t & 255) != 0: what cvttsd2si followed by taking the low byte gives. The C++ conversion
+ *   is defined on (-1, 256) only; outside that range this is a rule of ours and unpinned. So
+ *   a return with depth in [0, 1) or [256, 257) is invisible to the patch (yet counts for
+ *   min_v when positive), and a depth of -3.2 is seen.
+ * Per keypoint (:355-401), pt = (px, py) float: py < (float)min_v gives class 0, depth -1.0f.
+ *   Otherwise the cells of dx = -SQLM_LD_HALF_W .. SQLM_LD_HALF_W - 1 (outer loop),
+ *   dy = -SQLM_LD_HALF_H .. SQLM_LD_HALF_H - 1 (inner) are row = int(py + (float)dy),
+ *   col = int(px + (float)dx): the add in float, the conversion truncating toward zero (a sum
+ *   in (-1, 0) is cell 0, and px = 3.5 reaches column 0 with dx = -4 and with dx = -3). A cell
+ *   outside the image (a sum that is NaN, <= -1 or >= the size) is empty; the reference reads
+ *   out of bounds there, which its extractor rules out (keypoints stay 16 px inside,
+ *   ORBextractor.cc:1058-1061). Over the seen cells: min and max depth (the reference's sort
+ *   serves front() and back() only) and the nearest cell, the one of least key
+ *   (dx dx + dy dy, (dx + SQLM_LD_HALF_W) 2 SQLM_LD_HALF_H + (dy + SQLM_LD_HALF_H)): :373 is
+ *   strict, so among equal distances the first in scan order wins, and distinct small integers
+ *   have distinct double square roots, so comparing the integers equals comparing the sqrt.
+ *   No seen cell: class 0, depth -1. max - min > SQLM_LD_MAX_RANGE (double): class 2,
+ *   depth -1. Otherwise class 1 and depth = (float)image[nearest]. nearest_uv = (col, row) of
+ *   the nearest cell, (-1, -1) when there is none (classes 0) - it is reported for class 2 too.
+ *   n_with_depth counts keypoints with depth > 0 (:404-408).
+ * Camera-frame point (Frame::UnprojectStereo, :1710-1723), when key_un_xy (mvKeysUn[i].pt),
+ *   cam = (fx, fy, cx, cy) and xyz_cam are all given: for z = depth > 0, in float,
+ *   x = ((u - cx) z) (1.0f / fx), y = ((v - cy) z) (1.0f / fy), and z; zeros otherwise. The
+ *   world transform of :1725 is a cv::Mat float product whose rounding cannot be pinned here;
+ *   it stays with the caller. xyz_cam without key_un_xy or cam is SQLM_ERR_INVALID_ARG.
+ * A depth that overflows to a NaN (coordinates times matrix entries beyond double) is stored
+ *   as some NaN; it is never seen and never positive. No memory is touched out of bounds for
+ *   any finite or non-finite input.
+ *
+ * Empty sweeps, empty keypoint lists, frames with either one empty and n_frame = 0 are fine.
+ * Limits: rows, cols in [1, SQLM_LD_MAX_DIM], n_frame rows cols <= SQLM_LD_MAX_CELLS, fewer
+ * than 2^31 points and fewer than 2^27 keypoints in the batch: beyond them
+ * SQLM_ERR_UNSUPPORTED before the device (or any array) is touched. SQLM_ERR_INVALID_ARG: a
+ * NULL required pointer, n_frame < 0, rows or cols < 1, offsets that do not start at 0 or
+ * decrease, a sweep of 2^31 - 1 points or more, a non-finite matrix entry. */
+#define SQLM_LD_HALF_W 4        /* half_patch_width, :339 */
+#define SQLM_LD_HALF_H 7        /* half_patch_height, :340 */
+#define SQLM_LD_MIN_X 1.0f      /* :295, :308 */
+#define SQLM_LD_MAX_RANGE 2.0   /* :386 */
+#define SQLM_LD_MAX_DIM 4096
+#define SQLM_LD_MAX_CELLS (1 << 25)
+/* Outputs are packed like the inputs: keypoint k of the batch owns class_id[k], depth[k],
+ * nearest_uv[2k..], xyz_cam[3k..]. stats[f] = (min_v, n_written, n_occupied, n_with_depth).
+ * depth_image, when given, receives double [n_frame][rows][cols]; it is not read back from
+ * the device otherwise. */
+int sqlm_lidar_depth(sqlm_ctx *ctx, int n_frame, const int64_t *sweep_off /*[n_frame+1]*/,
+    const float *xyz /*[n][3]*/, const int64_t *key_off /*[n_frame+1]*/, const float *key_xy /*[m][2]*/,
+    const float *key_un_xy /*[m][2], NULL ok*/, int rows, int cols,
+    const double *intrinsic /*[12]*/, const double *extrinsic /*[16]*/, const float *cam /*[4], NULL ok*/,
+    int32_t *class_id /*[m]*/, float *depth /*[m]*/, int32_t *nearest_uv /*[m][2]*/,
+    float *xyz_cam /*[m][3], NULL ok*/, int32_t *stats /*[n_frame][4]*/, double *depth_image /*NULL ok*/);
+/* The same text compiled for the CPU; no context, no device. The two trailing arrays are the
+ * intermediate state (NULL ok): pixel [n] = v cols + u of a writing point, -1 otherwise;
+ * winner [n_frame][rows][cols] = the occupant's index within its sweep plus one, 0 = unwritten. */
+int sqlm_lidar_depth_host(int n_frame, const int64_t *sweep_off, const float *xyz,
+    const int64_t *key_off, const float *key_xy, const float *key_un_xy, int rows, int cols,
+    const double *intrinsic, const double *extrinsic, const float *cam,
+    int32_t *class_id, float *depth, int32_t *nearest_uv, float *xyz_cam, int32_t *stats,
+    double *depth_image, int32_t *pixel, int32_t *winner);
+/* The state of the context's last sqlm_lidar_depth, read back from the device, sized by that
+ * call's arguments; any pointer may be NULL. SQLM_ERR_STATE before any call. */
+int sqlm_lidar_depth_get_state(sqlm_ctx *ctx, int32_t *pixel, int32_t *winner, double *depth_image);
+/* out[0] = SQLM_LD_MAX_DIM, out[1] = SQLM_LD_MAX_CELLS, out[2] = kernel launches of the last
+ * call (0: nothing reached the device), out[3] = SQLM_LD_HALF_W, out[4] = SQLM_LD_HALF_H,
+ * out[5] = lanes per keypoint, out[6] = points and out[7] = keypoints of the last call
+ * (saturated at INT32_MAX). ctx may be NULL (the limits alone). */
+int sqlm_lidar_depth_info(const sqlm_ctx *ctx, int32_t out[8]);
+
 /* Results (write-back inputs, g2oOptimizer.cc:1167-1189, :306-360). */
 int sqlm_get_poses(sqlm_ctx *ctx, double *pose_q, double *pose_t);
 int sqlm_get_points(sqlm_ctx *ctx, double *pt);

@@ -153,6 +153,7 @@ int sqlm_ctx_destroy(sqlm_ctx *c) {
   if (c->bow) bow_destroy(c->bow);
   if (c->mappoint) mappoint_destroy(c->mappoint);
   if (c->lidar_feat) lidar_feat_destroy(c->lidar_feat);
+  if (c->lidar_depth) lidar_depth_destroy(c->lidar_depth);
   for (auto &b : c->bufs)
     if (b.p) (void)hipFree(b.p);
   for (auto &b : c->pins) free_pinned(b);

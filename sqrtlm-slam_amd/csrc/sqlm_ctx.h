@@ -102,6 +102,7 @@ struct sqlm_ctx {
   sqlm::BowSolver *bow = nullptr;  // staging of sqlm_bow_transform / sqlm_bow_score (sqlm_bow.cpp)
   sqlm::MapPointSolver *mappoint = nullptr;  // sqlm_triangulate_pairs / sqlm_map_points_update (sqlm_mappoint.cpp)
   sqlm::LidarFeatSolver *lidar_feat = nullptr;  // sqlm_lidar_features (sqlm_lidar_feat.cpp)
+  sqlm::LidarDepthSolver *lidar_depth = nullptr;  // sqlm_lidar_depth (sqlm_lidar_depth.cpp)
   // ---- timing ----
   hipEvent_t ev[2 * SQLM_NKERNEL_TIMERS] = {};
   // side stream: the camera pass runs concurrently with the landmark QR

@@ -813,4 +813,9 @@ void mappoint_destroy(MapPointSolver *s);
 struct LidarFeatSolver;
 void lidar_feat_destroy(LidarFeatSolver *s);
 
+// LiDAR depth image and keypoint depth association (sqlm_lidar_depth.cpp host, sqlm_lidar_depth.hip
+// kernels, lidar_depth_dev.h the arithmetic and the launch interface)
+struct LidarDepthSolver;
+void lidar_depth_destroy(LidarDepthSolver *s);
+
 }  // namespace sqlm

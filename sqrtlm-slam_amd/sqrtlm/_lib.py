@@ -61,6 +61,8 @@ EXPORTS = [
     # LiDAR flat-feature extraction (Frame::lidarProcess, flat-point path) and its host twin
     "sqlm_lidar_features", "sqlm_lidar_features_host", "sqlm_lidar_features_get_state", "sqlm_lidar_features_info",
     "sqlm_lidar_feat_trig_probe",
+    # LiDAR depth image and keypoint depth association (Frame.cc:290-313, :333-408) and its host twin
+    "sqlm_lidar_depth", "sqlm_lidar_depth_host", "sqlm_lidar_depth_get_state", "sqlm_lidar_depth_info",
 ]
 # every symbol include/sqrtlm_capture.h declares
 CAPTURE_EXPORTS = ["sqlm_capture_write", "sqlm_capture_read", "sqlm_capture_free", "sqlm_capture_replay",
@@ -228,6 +230,14 @@ def lib() -> C.CDLL:
             L.sqlm_lidar_features_get_state.argtypes = [P, P]
             L.sqlm_lidar_features_info.argtypes = [P, P]
             L.sqlm_lidar_feat_trig_probe.argtypes = [C.c_int64, P, P, P]
+        if hasattr(L, "sqlm_lidar_depth"):
+            P = C.c_void_p
+            # [ctx,] n_frame, sweep_off, xyz, key_off, key_xy, key_un_xy, rows, cols, intrinsic, extrinsic, cam,
+            # class_id, depth, nearest_uv, xyz_cam, stats, depth_image [, pixel, winner]
+            L.sqlm_lidar_depth.argtypes = [P, C.c_int] + [P] * 5 + [C.c_int, C.c_int] + [P] * 9
+            L.sqlm_lidar_depth_host.argtypes = [C.c_int] + [P] * 5 + [C.c_int, C.c_int] + [P] * 11
+            L.sqlm_lidar_depth_get_state.argtypes = [P, P, P, P]
+            L.sqlm_lidar_depth_info.argtypes = [P, P]
         if hasattr(L, "sqlm_triangulate_pairs"):
             P = C.c_void_p
             # [ctx,] n_pair, pairs, match_off, matches, [sweeps,] x3d, reason, n_new
