@@ -9,6 +9,7 @@
 #include <iostream>
 #include <vector>
 
+#include "hipFrameLidarDetail.h"
 #include "sqrtlm.h"
 
 namespace ORB_SLAM2 {
@@ -21,6 +22,10 @@ struct FrameCtxHolder {
     if (ctx) sqlm_ctx_destroy(ctx);
   }
 };
+
+}  // namespace
+
+namespace frame_lidar_detail {
 
 // one context per calling thread (Tracking's)
 sqlm_ctx* frame_thread_ctx() {
@@ -68,6 +73,12 @@ PointIRT MakePoint(const float* xyz, int row) {
   p.timestamp = 0.1;
   return p;
 }
+
+}  // namespace frame_lidar_detail
+
+namespace {
+
+using namespace frame_lidar_detail;
 
 bool Extract(Frame* pF, const double* extrinsic) {
   if (!pF || !pF->lidarconfig_ || !pF->lidar_inputPtr_) return false;

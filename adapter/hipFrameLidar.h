@@ -35,6 +35,17 @@ class hipFrameLidar {
   // runs lidarProcess. With using_flat_point off the members are left empty.
   static bool ExtractFlatFeatures(Frame* pF);
   static bool ExtractFlatFeatures(Frame* pF, const Eigen::Matrix<double, 4, 4>& extrinsicMatrix);
+
+  // Both branches of ExtractFeaturePoints in one sqlm_lidar_features_all call
+  // (hipFrameLidarCorner.cc), for either value of using_sharp_point: the flat
+  // members as ExtractFlatFeatures fills them (when using_flat_point) and, with
+  // using_sharp_point, corner_points_sharp_ and corner_points_less_sharp_, the
+  // latter with the segment label as intensity (Frame.cc:1016). False, with the
+  // frame untouched (the input cloud included), when the library call failed;
+  // the caller then runs lidarProcess. less_sharp_ and feature_state are not
+  // filled.
+  static bool ExtractFeatures(Frame* pF);
+  static bool ExtractFeatures(Frame* pF, const Eigen::Matrix<double, 4, 4>& extrinsicMatrix);
 };
 
 }  // namespace ORB_SLAM2

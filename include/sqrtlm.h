@@ -588,7 +588,7 @@ int sqlm_lidar_get_exec_info(sqlm_ctx *ctx, int out[8]);
  *
  * Limits: row_num in [1, 128], col_num in [1, 4096], the neighbourhood half-width
  * int(0.01 / (deg_diff / 180 PI) + 0.5) + 1 <= 8, using_sharp_point = 0 (the corner branch,
- * :861-1038, is a sequential region growing and is not built): beyond them
+ * :861-1038, is sqlm_lidar_features_all's, below): beyond them
  * SQLM_ERR_UNSUPPORTED, before the device is touched. num_scan_subregions < 1,
  * num_curvature_regions_flat < 1, a negative corner width or cap, deg_diff <= 0 and a sweep
  * of 2^31 points or more are SQLM_ERR_INVALID_ARG. */
@@ -655,6 +655,132 @@ int sqlm_lidar_features_info(const sqlm_ctx *ctx, int32_t out[8]);
 /* Test probe of sqlm_libm.h's atan / atan2 as this library compiled them: out[i] =
  * atan2 of (y[i], x[i]), or atan of y[i] where x is NULL. */
 int sqlm_lidar_feat_trig_probe(int64_t n, const double *y, const double *x, double *out);
+
+/* ---- LiDAR corner-feature extraction of a fusion frame ----
+ * The corner branch of Frame::ExtractFeaturePoints (src/data_structure/Frame.cc:861-1038 with
+ * PrepareRing_corner :647 and PrepareSubregion_corner :756; line numbers are that file's), beside
+ * the flat branch above: sqlm_lidar_features_all runs both on one range image. Ring assignment,
+ * columns, cell occupants, scan order and image_index are those of sqlm_lidar_features. Float
+ * and double expressions are evaluated as written with C++'s usual conversions, no FMA;
+ * acos / sin / cos / atan2 are sqlm_libm.h's.
+ *
+ * Cell state (int32 per range-image cell): -3 when unoccupied; -1 (ground) when the final
+ *   occupant has (double)z < ground_z_bound; else 0. :596-626 rewrite the state at every change
+ *   of occupant, so it follows the occupant of least distance and is order-free.
+ * Corner rings: ring r (0-based) takes part when corner_ring_enabled[r], which the caller
+ *   builds as lower_ring_num_sharp_point <= r + 1 && r < upper_ring_num_sharp_point, and when
+ *   its scan passes the short-scan test of the flat path (:846-854, the same min over both
+ *   widths).
+ * Corner mask (:647-701), c = num_curvature_regions_corner, for i in [c, n - c): the two
+ *   depth-jump rules of the flat mask with c ([i - c, i] or [i + 1, i + c]); only when neither
+ *   fired for i: mask[i] = 1 when (double)diff_next2 > 0.0002 (double)dis2 &&
+ *   (double)diff_prev2 > 0.0002 (double)dis2, with diff_next2 = CalcSquaredDiff(p_i, p_i+1),
+ *   diff_prev2 = CalcSquaredDiff(p_i, p_i-1), dis2 = (x x + y y) + z z in float. The mask is
+ *   the OR of every i's writes.
+ * Corner curvature (:766-780): half-width c always; dx = -(float)(2c) x, then
+ *   dx += x[i + j] + x[i - j] for j = 1 .. c (likewise y, z), curvature =
+ *   ((dx dx + dy dy) + dz dz) / (float)(2c). Subregion j is [sp, ep] of :871-874 (the flat
+ *   formula with c), skipped when ep <= sp. Its candidates are sorted ascending on
+ *   (curvature bits, index) and walked from the highest rank down: among equal curvatures the
+ *   higher index comes first.
+ * Edge predicate between two occupied, non-ground cells with occupants p1, p2 (:963-975), in
+ *   double: n = sqrt((x x + y y) + z z), dot = (x1 x2 + y1 y2) + z1 z2 (Eigen's own summation
+ *   order is unpinned); d1 = (float)max(n1, n2), d2 = (float)min(n1, n2);
+ *   alpha = (float)acos(dot / (n1 n2));
+ *   angle = (float)atan2((double)(d2 sinf(alpha)), (double)(d1 - d2 cosf(alpha))) with
+ *   sinf(a) = (float)sin((double)a), cosf likewise, the products and the difference in float.
+ *   The edge exists when angle > 1.0f; a NaN (an acos argument that rounds above 1) gives no
+ *   edge. The predicate is bit-symmetric in its cells.
+ * Neighbourhood (:929-957), directed, six distinct offsets (row, col) numbered
+ *   0 (-1, 0), 1 (1, 0), 2 (0, -1), 3 (0, 1), 4 (-1, -1), 5 (1, -1). A row outside
+ *   [0, row_num) has no target; a column < 0 becomes col_num - 1, one >= col_num becomes 0.
+ *   A cell's edge mask has bit k set when offset k has a target, both cells are occupied and
+ *   not ground, and the edge exists.
+ * Growth from a seed cell of state 0: S = the cells reachable from the seed along edge-mask
+ *   bits through cells whose state is 0 when the growth starts, the seed included (the set does
+ *   not depend on the traversal). lineCount = the number of distinct rows among S \ {seed}
+ *   (:980 flags the row of every pushed cell, never the seed's own push). lineCount >= 3: every
+ *   cell of S gets the current label and the label counter, 1 at the start of each sweep, goes
+ *   up by one. Otherwise every cell of S becomes -2.
+ * Walk (:861-1037), per sweep, corner rings ascending, subregions ascending, ranks descending,
+ *   num = 0 per subregion. Per candidate: cell state -1 -> GROUND. Else mask set -> MASKED;
+ *   else !((double)curvature > sharp_curv_th) -> CURVATURE. Else, if the cell state is 0, grow
+ *   from it; if the state is then < 1 -> UNSTABLE (whether the -2 is this growth's or an
+ *   earlier one's; a cell an earlier seed labelled passes without growing). Else, if
+ *   num < max_corner_less_sharp, the point is PICKED: a less-sharp point with its cell's
+ *   label, a sharp point too if num < max_corner_sharp, ++num; with a cap of 0 it is OVER_CAP.
+ *   If then num >= max_corner_less_sharp the subregion stops: every lower rank is OVER_CAP
+ *   whatever its own evaluation would give, and is not grown.
+ * Outputs per sweep in push order, through `extrinsic` as the flat clouds: sharp xyz;
+ *   less-sharp xyz, label (what :1016 leaves in the point's intensity) and (row, col).
+ *   less_sharp_ and feature_state are not provided (nothing outside that loop reads them), nor
+ *   is the label :1016 leaves in the intensity of flat points inside a picked segment.
+ * The flat branch reads point_state only as != -3 and the corner branch never makes or
+ *   removes a -3, so the flat outputs do not depend on the corner branch. */
+#define SQLM_LC_NONE 0
+#define SQLM_LC_GROUND 1
+#define SQLM_LC_MASKED 2
+#define SQLM_LC_CURVATURE 3
+#define SQLM_LC_UNSTABLE 4
+#define SQLM_LC_OVER_CAP 5
+#define SQLM_LC_PICKED 6
+typedef struct sqlm_lidar_corner_params {
+  int32_t max_corner_sharp, max_corner_less_sharp;
+  double sharp_curv_th, ground_z_bound;
+  uint8_t corner_ring_enabled[SQLM_LF_MAX_ROWS];
+} sqlm_lidar_corner_params;
+
+/* The intermediate state of the corner branch. Caller-allocated; any pointer may be NULL.
+ * Scan points are numbered as in sqlm_lidar_feat_state, whose scan_off applies. */
+typedef struct sqlm_lidar_corner_state {
+  int32_t *cell_state; /* [S][col_num] final: -3, -2, -1, 0 or a label */
+  uint8_t *mask;       /* [n] the corner mask, 0 on a row that takes no part */
+  float *curvature;    /* [n] 0 outside the corner subregions */
+  int32_t *sorted;     /* [n] as sqlm_lidar_feat_state.sorted, ascending rank */
+  uint8_t *reason;     /* [n] SQLM_LC_* */
+  uint8_t *edge;       /* [S][col_num] the 6-bit edge mask */
+  float *angle;        /* [S][col_num][6] the angle of every offset; NaN where the offset has no
+                          target or either cell is unoccupied or ground */
+} sqlm_lidar_corner_state;
+
+/* Both branches on one upload and one range image. The flat outputs are those of
+ * sqlm_lidar_features; when all seven are NULL the flat stage is skipped. params->using_sharp_point
+ * is ignored. corner == NULL runs no corner stage (the six corner outputs are not touched) and
+ * equals sqlm_lidar_features bit for bit. The corner arrays have room for n entries, the offsets
+ * for n_sweep + 1. Limits as sqlm_lidar_features; with corner != NULL,
+ * num_curvature_regions_corner < 1, a negative cap and a non-finite threshold or ground bound
+ * are SQLM_ERR_INVALID_ARG, reported before the device is touched. */
+int sqlm_lidar_features_all(sqlm_ctx *ctx, int n_sweep, const int64_t *sweep_off, const float *xyz,
+    const sqlm_lidar_feat_params *params, const sqlm_lidar_corner_params *corner,
+    const double *extrinsic,
+    int64_t *flat_off, float *flat_xyz, float *flat_normal,
+    int64_t *less_off, float *less_xyz, float *less_normal, int32_t *less_row_col,
+    int64_t *sharp_off /*[n_sweep+1]*/, float *sharp_xyz /*[n][3]*/,
+    int64_t *less_sharp_off /*[n_sweep+1]*/, float *less_sharp_xyz /*[n][3]*/,
+    int32_t *less_sharp_label /*[n]*/, int32_t *less_sharp_row_col /*[n][2]*/);
+/* The same text on the CPU; either state may be NULL. */
+int sqlm_lidar_features_all_host(int n_sweep, const int64_t *sweep_off, const float *xyz,
+    const sqlm_lidar_feat_params *params, const sqlm_lidar_corner_params *corner,
+    const double *extrinsic,
+    int64_t *flat_off, float *flat_xyz, float *flat_normal,
+    int64_t *less_off, float *less_xyz, float *less_normal, int32_t *less_row_col,
+    int64_t *sharp_off, float *sharp_xyz, int64_t *less_sharp_off, float *less_sharp_xyz,
+    int32_t *less_sharp_label, int32_t *less_sharp_row_col,
+    sqlm_lidar_feat_state *flat_state, sqlm_lidar_corner_state *corner_state);
+/* The state of the context's last sqlm_lidar_features_all, read back from the device; either
+ * may be NULL. The angle array is recomputed by a launch of its own. corner_state after a call
+ * without a corner stage is SQLM_ERR_STATE. */
+int sqlm_lidar_features_all_get_state(sqlm_ctx *ctx, sqlm_lidar_feat_state *flat_state,
+    sqlm_lidar_corner_state *corner_state);
+/* Of the last sqlm_lidar_features_all: out[0] = kernel launches, out[1] = seeds grown,
+ * out[2] = cells labelled, out[3] = cells set unstable, out[4] = the largest segment (cells of
+ * one growth), out[5] = the most BFS levels of one growth, out[6] = less-sharp points,
+ * out[7] = sharp points. */
+int sqlm_lidar_features_all_info(const sqlm_ctx *ctx, int32_t out[8]);
+/* Test probe of sqlm_libm.h's acos (which = 0), sin (1) and cos (2) as this library compiled them. */
+int sqlm_lidar_corner_trig_probe(int64_t n, int which, const double *x, double *out);
+/* Test probe of the edge predicate: out[i] = the float angle of p1[i], p2[i] (float xyz). */
+int sqlm_lidar_corner_angle_probe(int64_t n, const float *p1, const float *p2, float *out);
 
 /* ---- LiDAR depth image and keypoint depth association of a fusion frame ----
  * The other LiDAR half of the reference's Frame constructor

@@ -25,7 +25,9 @@
 #include "../../include/sqlm_libm.h"
 #include "../../include/sqrtlm.h"
 
+#if defined(__clang__)
 #pragma clang fp contract(off)
+#endif
 
 namespace sqlm {
 
@@ -71,9 +73,6 @@ struct LfDev {
   float *flat_xyz = nullptr, *flat_normal = nullptr, *less_xyz = nullptr, *less_normal = nullptr;
   int32_t *less_rc = nullptr;
 };
-
-// The launches of one call, in order; returns how many kernels were launched.
-int launch_lidar_feat(const LfDev &d, hipStream_t st);
 
 SQLM_HD inline uint32_t lf_bits(float v) {
   union {
@@ -337,5 +336,43 @@ SQLM_HD inline void lf_transform(const double *ext, const float *p, float *out) 
     out[k] = (float)(((m[0] * (double)p[0] + m[1] * (double)p[1]) + m[2] * (double)p[2]) + m[3]);
   }
 }
+
+#if defined(__HIPCC__)
+// Device helpers the kernels of sqlm_lidar_feat.hip and sqlm_lidar_corner.hip share
+// ascending bitonic sort of key[0 .. npow) by the whole workgroup; npow a power of two
+__device__ __forceinline__ void lf_sort(unsigned long long *key, int npow) {
+  for (int k = 2; k <= npow; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < npow; i += kLfBlock) {
+        const int l = i ^ j;
+        if (l > i) {
+          const unsigned long long a = key[i], b = key[l];
+          if ((a > b) == ((i & k) == 0)) {
+            key[i] = b;
+            key[l] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ int lf_pow2(int n) {
+  int p = 2;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+__device__ __forceinline__ void lf_put(const LfDev &d, const float *p, float *out) {
+  if (d.has_ext) {
+    lf_transform(d.ext, p, out);
+  } else {
+    out[0] = p[0];
+    out[1] = p[1];
+    out[2] = p[2];
+  }
+}
+#endif
 
 }  // namespace sqlm

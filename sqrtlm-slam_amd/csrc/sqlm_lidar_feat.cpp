@@ -1,17 +1,19 @@
-// sqlm_lidar_feat.cpp — host side of sqlm_lidar_features: argument and limit
+// sqlm_lidar_feat.cpp — host side of sqlm_lidar_features and of
+// sqlm_lidar_features_all (the flat branch and the corner branch on one range
+// image; corner kernels: sqlm_lidar_corner.hip): argument and limit
 // checks before the device is touched, one staged upload, the launches
 // (sqlm_lidar_feat.hip), the read-back of the packed outputs; the read-back of
 // the intermediate state for tests; and sqlm_lidar_features_host, the host
 // twin: the reference's loops run sequentially over the same text
-// (lidar_feat_dev.h) compiled for the CPU. Built with -ffp-contract=off like
-// the kernels.
+// (lidar_feat_dev.h, lidar_corner_dev.h) compiled for the CPU. Built with
+// -ffp-contract=off like the kernels.
 #include <algorithm>
 #include <cstring>
 #include <limits>
 #include <new>
 #include <vector>
 
-#include "lidar_feat_dev.h"
+#include "lidar_feat_host.h"
 #include "sqlm_ctx.h"
 #include "sqlm_staging.h"
 
@@ -24,87 +26,15 @@ struct LidarFeatSolver {
   LfDev d;              // the last call's device pointers
   bool have = false;    // a call has completed
   int32_t launches = 0, stats[4] = {0, 0, 0, 0};
+  LcDev lc;                  // the corner stage of the last sqlm_lidar_features_all
+  bool have_corner = false;  // that call ran one
+  int32_t cstats[5] = {0, 0, 0, 0, 0};
+  int64_t n_less_sharp = 0, n_sharp = 0;
 };
 
 void lidar_feat_destroy(LidarFeatSolver *s) { delete s; }
 
 namespace {
-
-// The checks every entry point shares; fills `p` when they pass.
-int lf_check(int n_sweep, const int64_t *sweep_off, const float *xyz, const sqlm_lidar_feat_params *prm,
-             const void *const *outs, int n_outs, LfParams *p) {
-  if (n_sweep < 0 || !sweep_off || !prm || sweep_off[0] != 0) return SQLM_ERR_INVALID_ARG;
-  for (int s = 0; s < n_sweep; ++s) {
-    if (sweep_off[s + 1] < sweep_off[s]) return SQLM_ERR_INVALID_ARG;
-    if (sweep_off[s + 1] - sweep_off[s] >= (int64_t)std::numeric_limits<int32_t>::max()) return SQLM_ERR_INVALID_ARG;
-  }
-  const int64_t n = sweep_off[n_sweep];
-  if (!outs[0] || !outs[1]) return SQLM_ERR_INVALID_ARG;  // the offset arrays
-  if (n > 0) {
-    if (!xyz) return SQLM_ERR_INVALID_ARG;
-    for (int k = 2; k < n_outs; ++k)
-      if (!outs[k]) return SQLM_ERR_INVALID_ARG;
-  }
-  if (prm->num_scan_subregions < 1 || prm->num_curvature_regions_flat < 1 || prm->num_curvature_regions_corner < 0 ||
-      prm->max_surf_flat < 0 || prm->max_surf_less_flat < 0 || !(prm->deg_diff > 0.0) || prm->row_num < 1 ||
-      prm->col_num < 1)
-    return SQLM_ERR_INVALID_ARG;
-  if (prm->using_sharp_point != 0) return SQLM_ERR_UNSUPPORTED;
-  if (prm->row_num > SQLM_LF_MAX_ROWS || prm->col_num > SQLM_LF_MAX_COLS) return SQLM_ERR_UNSUPPORTED;
-  const double hw = 0.01 / (prm->deg_diff / 180.0 * kLfPi) + 0.5;
-  if (!(hw + 1.0 < (double)(kLfMaxHalf + 1))) return SQLM_ERR_UNSUPPORTED;
-  if ((int64_t)n_sweep * prm->row_num * prm->num_scan_subregions >= (1ll << 30)) return SQLM_ERR_INVALID_ARG;
-  if (prm->num_curvature_regions_flat > SQLM_LF_MAX_COLS || prm->num_curvature_regions_corner > SQLM_LF_MAX_COLS)
-    return SQLM_ERR_INVALID_ARG;
-  p->row_num = prm->row_num;
-  p->col_num = prm->col_num;
-  p->n_sub = prm->num_scan_subregions;
-  p->ncr = prm->num_curvature_regions_flat;
-  p->min_scan = 2 * std::max(prm->num_curvature_regions_flat, prm->num_curvature_regions_corner) + 1;
-  p->max_flat = prm->max_surf_flat;
-  p->max_less = prm->max_surf_less_flat;
-  p->curv_th = prm->surf_curv_th;
-  p->max_sq_dis = prm->max_sq_dis;
-  p->deg_diff = prm->deg_diff;
-  std::memcpy(p->ring_enabled, prm->ring_enabled, sizeof(p->ring_enabled));
-  return SQLM_OK;
-}
-
-// The per-scan-point arrays as both sides hold them: [n_rows][col_num]
-struct LfStrided {
-  const int32_t *scan_n, *scan_src, *scan_col, *image_index, *nbr, *sorted;
-  const uint8_t *mask, *reason;
-  const float *curv;
-};
-
-void lf_pack_state(const LfParams &p, int n_rows, int64_t n, const int32_t *ring, const LfStrided &a,
-                   sqlm_lidar_feat_state *st) {
-  if (st->ring && n) std::memcpy(st->ring, ring, (size_t)n * sizeof(int32_t));
-  if (st->image_index && n_rows)
-    std::memcpy(st->image_index, a.image_index, (size_t)n_rows * p.col_num * sizeof(int32_t));
-  int64_t off = 0;
-  for (int q = 0; q < n_rows; ++q) {
-    if (st->scan_off) st->scan_off[q] = off;
-    const int m = a.scan_n[q];
-    const size_t b = (size_t)q * p.col_num;
-    if (st->scan_src) std::copy(a.scan_src + b, a.scan_src + b + m, st->scan_src + off);
-    if (st->scan_col) std::copy(a.scan_col + b, a.scan_col + b + m, st->scan_col + off);
-    if (st->mask) std::copy(a.mask + b, a.mask + b + m, st->mask + off);
-    if (st->curvature) std::copy(a.curv + b, a.curv + b + m, st->curvature + off);
-    if (st->neighbours) std::copy(a.nbr + b, a.nbr + b + m, st->neighbours + off);
-    if (st->sorted) std::copy(a.sorted + b, a.sorted + b + m, st->sorted + off);
-    if (st->reason) std::copy(a.reason + b, a.reason + b + m, st->reason + off);
-    off += m;
-  }
-  if (st->scan_off) st->scan_off[n_rows] = off;
-}
-
-void lf_put_host(const double *ext, const float *p, float *out) {
-  if (ext)
-    lf_transform(ext, p, out);
-  else
-    std::memcpy(out, p, 3 * sizeof(float));
-}
 
 int lf_solver(sqlm_ctx *c) {
   if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
@@ -112,194 +42,20 @@ int lf_solver(sqlm_ctx *c) {
   return SQLM_OK;
 }
 
-}  // namespace
-
-}  // namespace sqlm
-
-using namespace sqlm;
-
-extern "C" {
-
-int sqlm_lidar_features_host(int n_sweep, const int64_t *sweep_off, const float *xyz,
-                             const sqlm_lidar_feat_params *params, const double *extrinsic, int64_t *flat_off,
-                             float *flat_xyz, float *flat_normal, int64_t *less_off, float *less_xyz,
-                             float *less_normal, int32_t *less_row_col, sqlm_lidar_feat_state *state) {
-  LfParams p;
-  const void *outs[7] = {flat_off, less_off, flat_xyz, flat_normal, less_xyz, less_normal, less_row_col};
-  if (int r = lf_check(n_sweep, sweep_off, xyz, params, outs, 7, &p)) return r;
-  const int64_t n = sweep_off[n_sweep];
-  const int rows = p.row_num, cols = p.col_num, n_rows = n_sweep * rows;
-  const size_t cells = (size_t)n_rows * cols;
-  std::vector<int32_t> ring((size_t)n, -1), scan_n((size_t)n_rows, 0), scan_src(cells, 0), scan_col(cells, 0),
-      image_index(cells, -1), nbr(cells, 0), sorted(cells, -1);
-  std::vector<uint8_t> mask(cells, 0), reason(cells, 0);
-  std::vector<float> curv(cells, 0.f), scan_xyz(3 * cells, 0.f), azi;
-  std::vector<unsigned long long> cell_key, keys;
-  std::vector<uint32_t> cell_first;
-  int64_t n_flat = 0, n_less = 0;
-  for (int s = 0; s < n_sweep; ++s) {
-    flat_off[s] = n_flat;
-    less_off[s] = n_less;
-    const int64_t o = sweep_off[s];
-    const int32_t ns = (int32_t)(sweep_off[s + 1] - o);
-    const float *P = xyz + 3 * o;
-    azi.assign((size_t)ns, 0.f);
-    int32_t first = -1, last = -1;
-    for (int32_t i = 0; i < ns; ++i) {
-      const float x = P[3 * i], y = P[3 * i + 1], z = P[3 * i + 2];
-      if (!(lf_finite(x) && lf_finite(y) && lf_finite(z))) continue;
-      const int rg = lf_ring(x, y, z);
-      ring[(size_t)(o + i)] = rg;
-      if (rg < 0) continue;
-      azi[i] = -lf_atan2f(y, x);
-      if (first < 0) first = i;
-      last = i;
-    }
-    if (first < 0) continue;
-    float start, end;
-    lf_oris(azi[first], azi[last], &start, &end);
-    const size_t sbase = (size_t)s * rows * cols;
-    cell_key.assign((size_t)rows * cols, ~0ull);
-    cell_first.assign((size_t)rows * cols, kLfNoIndex);
-    bool half = false;  // PointToImage's loop, state and all
-    for (int32_t i = 0; i < ns; ++i) {
-      const int rg = ring[(size_t)(o + i)];
-      if (rg < 0) continue;
-      float a;
-      if (!half) {
-        a = lf_unpassed(azi[i], start);
-        if (lf_turns_half(a, start)) half = true;
-      } else {
-        a = lf_passed(azi[i], end);
-      }
-      const int col = lf_col(a, start, cols);
-      if (col < 0 || rg >= rows) continue;
-      const size_t cell = (size_t)rg * cols + col;
-      const unsigned long long key = ((unsigned long long)lf_bits(lf_dist(P + 3 * i)) << 32) | (uint32_t)i;
-      if (key < cell_key[cell]) cell_key[cell] = key;
-      if ((uint32_t)i < cell_first[cell]) cell_first[cell] = (uint32_t)i;
-    }
-    for (int r = 0; r < rows; ++r) {
-      const size_t base = sbase + (size_t)r * cols;
-      keys.clear();
-      for (int c = 0; c < cols; ++c) {
-        const uint32_t f = cell_first[(size_t)r * cols + c];
-        if (f != kLfNoIndex) keys.push_back(((unsigned long long)f << 12) | (unsigned)c);
-      }
-      std::sort(keys.begin(), keys.end());
-      const int m = (int)keys.size();
-      scan_n[(size_t)s * rows + r] = m;
-      for (int q = 0; q < m; ++q) {
-        const int c = (int)(keys[q] & 4095u);
-        const uint32_t occ = (uint32_t)(cell_key[(size_t)r * cols + c] & 0xffffffffull);
-        scan_src[base + q] = (int32_t)occ;
-        scan_col[base + q] = c;
-        std::memcpy(&scan_xyz[3 * (base + q)], P + 3 * (size_t)occ, 3 * sizeof(float));
-        image_index[base + c] = q;
-      }
-      if (!p.ring_enabled[r] || m <= p.min_scan) continue;
-      const float *scan = &scan_xyz[3 * base];
-      for (int i = p.ncr; i + p.ncr < m; ++i) {
-        const int rule = lf_mask_rule(scan, i);
-        if (rule == 1)
-          std::fill_n(&mask[base + i - p.ncr], p.ncr + 1, (uint8_t)1);
-        else if (rule == 2)
-          std::fill_n(&mask[base + i + 1], p.ncr, (uint8_t)1);
-      }
-    }
-    LfView v;
-    v.image_index = &image_index[sbase];
-    v.scan_xyz = &scan_xyz[3 * sbase];
-    v.scan_col = &scan_col[sbase];
-    v.row_num = rows;
-    v.col_num = cols;
-    for (int r = 0; r < rows; ++r) {
-      const size_t base = sbase + (size_t)r * cols;
-      const int m = scan_n[(size_t)s * rows + r];
-      if (!p.ring_enabled[r] || m <= p.min_scan) continue;
-      const float *scan = &scan_xyz[3 * base];
-      for (int j = 0; j < p.n_sub; ++j) {
-        int64_t sp, ep;
-        lf_region(m, p.ncr, p.n_sub, j, &sp, &ep);
-        if (ep <= sp) continue;
-        const int size = (int)(ep - sp + 1);
-        keys.resize((size_t)size);
-        for (int k = 0; k < size; ++k) {
-          const int i = (int)sp + k;
-          int nb;
-          const float cv = lf_curvature(scan, i, m, p.ncr, &nb);
-          curv[base + i] = cv;
-          nbr[base + i] = nb;
-          keys[k] = ((unsigned long long)lf_bits(cv) << 32) | (unsigned)i;
-        }
-        std::sort(keys.begin(), keys.end());
-        int picked = 0, k = 0;
-        for (; k < size; ++k) {  // :1070-1233, the break included
-          const int idx = (int)(keys[k] & 0xffffffffull);
-          sorted[base + sp + k] = idx;
-          if (mask[base + idx]) {
-            reason[base + idx] = SQLM_LF_MASKED;
-            continue;
-          }
-          if (!((double)curv[base + idx] < p.curv_th)) {
-            reason[base + idx] = SQLM_LF_CURVATURE;
-            continue;
-          }
-          float nrm[3];
-          const int code = lf_candidate(v, p, r, idx, nrm);
-          reason[base + idx] = (uint8_t)code;
-          if (code != SQLM_LF_PICKED) continue;
-          if (picked < p.max_less) {
-            lf_put_host(extrinsic, scan + 3 * idx, less_xyz + 3 * n_less);
-            lf_put_host(extrinsic, nrm, less_normal + 3 * n_less);
-            less_row_col[2 * n_less] = r;
-            less_row_col[2 * n_less + 1] = scan_col[base + idx];
-            ++n_less;
-            if (picked < p.max_flat) {
-              lf_put_host(extrinsic, scan + 3 * idx, flat_xyz + 3 * n_flat);
-              lf_put_host(extrinsic, nrm, flat_normal + 3 * n_flat);
-              ++n_flat;
-            }
-            ++picked;
-          } else {
-            reason[base + idx] = SQLM_LF_OVER_CAP;
-          }
-          if (picked >= p.max_less) {
-            ++k;
-            break;
-          }
-        }
-        for (; k < size; ++k) {
-          const int idx = (int)(keys[k] & 0xffffffffull);
-          sorted[base + sp + k] = idx;
-          reason[base + idx] = SQLM_LF_OVER_CAP;
-        }
-      }
-    }
-  }
-  flat_off[n_sweep] = n_flat;
-  less_off[n_sweep] = n_less;
-  if (state) {
-    LfStrided a{scan_n.data(), scan_src.data(), scan_col.data(), image_index.data(), nbr.data(),
-                sorted.data(), mask.data(),     reason.data(),   curv.data()};
-    lf_pack_state(p, n_rows, n, ring.data(), a, state);
-  }
-  return SQLM_OK;
-}
-
-int sqlm_lidar_features(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, const float *xyz,
-                        const sqlm_lidar_feat_params *params, const double *extrinsic, int64_t *flat_off,
-                        float *flat_xyz, float *flat_normal, int64_t *less_off, float *less_xyz, float *less_normal,
-                        int32_t *less_row_col) {
-  if (!c) return SQLM_ERR_INVALID_ARG;
-  LfParams p;
-  const void *outs[7] = {flat_off, less_off, flat_xyz, flat_normal, less_xyz, less_normal, less_row_col};
-  if (int r = lf_check(n_sweep, sweep_off, xyz, params, outs, 7, &p)) return r;
+// The device side of both branches: `p` has passed lf_check (and `lc`, when
+// not null, lc_check); do_flat = the flat outputs exist.
+int lf_run(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, const float *xyz, const LfParams &p,
+           const double *extrinsic, bool do_flat, int64_t *flat_off, float *flat_xyz, float *flat_normal,
+           int64_t *less_off, float *less_xyz, float *less_normal, int32_t *less_row_col, const LcParams *lc,
+           const LcOut &co) {
   if (int r = lf_solver(c)) return r;
   LidarFeatSolver *s = c->lidar_feat;
   s->have = false;
+  s->have_corner = false;
   s->launches = 0;
+  s->n_less_sharp = s->n_sharp = 0;
   std::memset(s->stats, 0, sizeof(s->stats));
+  std::memset(s->cstats, 0, sizeof(s->cstats));
   const int64_t n = sweep_off[n_sweep];
   const size_t np = (size_t)n, ns = (size_t)n_sweep, n_rows = ns * p.row_num, cells = n_rows * p.col_num,
                regions = n_rows * p.n_sub;
@@ -309,9 +65,16 @@ int sqlm_lidar_features(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, cons
   d.n_sweep = n_sweep;
   d.n_rows = (int32_t)n_rows;
   d.n = n;
+  s->lc = LcDev();
   if (n == 0) {
-    for (int k = 0; k <= n_sweep; ++k) flat_off[k] = less_off[k] = 0;
+    for (int k = 0; k <= n_sweep; ++k) {
+      if (do_flat) flat_off[k] = less_off[k] = 0;
+      if (lc) co.sharp_off[k] = co.less_off[k] = 0;
+    }
+    s->lc.f = d;
+    if (lc) s->lc.p = *lc;
     s->have = true;
+    s->have_corner = lc != nullptr;
     return SQLM_OK;
   }
   d.has_ext = extrinsic ? 1 : 0;
@@ -328,11 +91,43 @@ int sqlm_lidar_features(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, cons
                z_curv = zeros.take(cells * 4), z_normal = zeros.take(cells * 12), z_mask = zeros.take(cells),
                z_reason = zeros.take(cells), z_nbr = zeros.take(cells * 4), z_ord = zeros.take(cells * 4),
                z_cnt = zeros.take(regions * 4), z_rl = zeros.take(regions * 8), z_rf = zeros.take(regions * 8);
+  // the corner stage's work: its sorted order in the first part, the rest zeroed
+  size_t c_sorted = 0, c_state = 0, c_edge = 0, c_mask = 0, c_reason = 0, c_curv = 0, c_cand = 0, c_cand_n = 0,
+         c_queue = 0, c_ord = 0, c_label = 0, c_cnt = 0, c_rl = 0, c_rs = 0;
+  if (lc) {
+    c_sorted = ones.take(cells * 4);
+    c_state = zeros.take(cells * 4);
+    c_edge = zeros.take(cells);
+    c_mask = zeros.take(cells);
+    c_reason = zeros.take(cells);
+    c_curv = zeros.take(cells * 4);
+    c_cand = zeros.take(cells * 4);
+    c_cand_n = zeros.take(regions * 4);
+    c_queue = zeros.take(cells * 4);
+    c_ord = zeros.take(cells * 4);
+    c_label = zeros.take(cells * 4);
+    c_cnt = zeros.take(regions * 4);
+    c_rl = zeros.take(regions * 8);
+    c_rs = zeros.take(regions * 8);
+  }
   // out: the small part first, read back before the clouds
   const size_t o_foff = out.take((ns + 1) * 8), o_loff = out.take((ns + 1) * 8), o_stats = out.take(16);
+  size_t o_csoff = 0, o_cloff = 0, o_cstats = 0;
+  if (lc) {
+    o_csoff = out.take((ns + 1) * 8);
+    o_cloff = out.take((ns + 1) * 8);
+    o_cstats = out.take(sizeof(s->cstats));
+  }
   const size_t o_small = out.off;
   const size_t o_fx = out.take(np * 12), o_fn = out.take(np * 12), o_lx = out.take(np * 12), o_ln = out.take(np * 12),
                o_rc = out.take(np * 8);
+  size_t o_csx = 0, o_clx = 0, o_clab = 0, o_crc = 0;
+  if (lc) {
+    o_csx = out.take(np * 12);
+    o_clx = out.take(np * 12);
+    o_clab = out.take(np * 4);
+    o_crc = out.take(np * 8);
+  }
   if (int r = s->in.grow(in.off)) return r;
   if (int r = s->work.grow(ones.off + zeros.off, false)) return r;
   if (int r = s->out.grow(out.off)) return r;
@@ -375,16 +170,62 @@ int sqlm_lidar_features(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, cons
   d.less_xyz = at<float>(od, o_lx);
   d.less_normal = at<float>(od, o_ln);
   d.less_rc = at<int32_t>(od, o_rc);
-  s->launches = launch_lidar_feat(d, c->stream);
+  s->launches = launch_lidar_feat_image(d, c->stream);
+  if (do_flat) s->launches += launch_lidar_feat_flat(d, c->stream);
+  LcDev &e = s->lc;
+  e.f = d;
+  if (lc) {
+    e.p = *lc;
+    e.sorted = at<int32_t>(w1, c_sorted);
+    e.state = at<int32_t>(w0, c_state);
+    e.edge = at<uint8_t>(w0, c_edge);
+    e.mask = at<uint8_t>(w0, c_mask);
+    e.reason = at<uint8_t>(w0, c_reason);
+    e.curv = at<float>(w0, c_curv);
+    e.cand = at<int32_t>(w0, c_cand);
+    e.cand_n = at<int32_t>(w0, c_cand_n);
+    e.queue = at<int32_t>(w0, c_queue);
+    e.ord = at<int32_t>(w0, c_ord);
+    e.label = at<int32_t>(w0, c_label);
+    e.region_cnt = at<int32_t>(w0, c_cnt);
+    e.region_less = at<int64_t>(w0, c_rl);
+    e.region_sharp = at<int64_t>(w0, c_rs);
+    e.sharp_off = at<int64_t>(od, o_csoff);
+    e.less_off = at<int64_t>(od, o_cloff);
+    e.stats = at<int32_t>(od, o_cstats);
+    e.sharp_xyz = at<float>(od, o_csx);
+    e.less_xyz = at<float>(od, o_clx);
+    e.less_label = at<int32_t>(od, o_clab);
+    e.less_rc = at<int32_t>(od, o_crc);
+    s->launches += launch_lidar_corner(e, c->stream);
+  }
   SQLM_HIP_OK(hipGetLastError());
   SQLM_HIP_OK(hipMemcpyAsync(s->out.host, s->out.dev, o_small, hipMemcpyDeviceToHost, c->stream));
   SQLM_HIP_OK(hipStreamSynchronize(c->stream));
   char *oh = s->out.host;
-  std::memcpy(flat_off, oh + o_foff, (ns + 1) * 8);
-  std::memcpy(less_off, oh + o_loff, (ns + 1) * 8);
-  std::memcpy(s->stats, oh + o_stats, 16);
-  const int64_t kf = flat_off[n_sweep], kl = less_off[n_sweep];
+  int64_t kf = 0, kl = 0, ks = 0, kc = 0;
+  if (do_flat) {
+    std::memcpy(flat_off, oh + o_foff, (ns + 1) * 8);
+    std::memcpy(less_off, oh + o_loff, (ns + 1) * 8);
+    std::memcpy(s->stats, oh + o_stats, 16);
+    kf = flat_off[n_sweep];
+    kl = less_off[n_sweep];
+  }
+  if (lc) {
+    std::memcpy(co.sharp_off, oh + o_csoff, (ns + 1) * 8);
+    std::memcpy(co.less_off, oh + o_cloff, (ns + 1) * 8);
+    std::memcpy(s->cstats, oh + o_cstats, sizeof(s->cstats));
+    ks = co.sharp_off[n_sweep];
+    kc = co.less_off[n_sweep];
+  }
   if (kf < 0 || kl < 0 || kf > n || kl > n) return SQLM_ERR_HIP;  // never: a scan point is picked once
+  if (ks < 0 || kc < 0 || ks > n || kc > n) return SQLM_ERR_HIP;
+  if (ks) SQLM_HIP_OK(hipMemcpyAsync(oh + o_csx, od + o_csx, (size_t)ks * 12, hipMemcpyDeviceToHost, c->stream));
+  if (kc) {
+    SQLM_HIP_OK(hipMemcpyAsync(oh + o_clx, od + o_clx, (size_t)kc * 12, hipMemcpyDeviceToHost, c->stream));
+    SQLM_HIP_OK(hipMemcpyAsync(oh + o_clab, od + o_clab, (size_t)kc * 4, hipMemcpyDeviceToHost, c->stream));
+    SQLM_HIP_OK(hipMemcpyAsync(oh + o_crc, od + o_crc, (size_t)kc * 8, hipMemcpyDeviceToHost, c->stream));
+  }
   if (kf) {
     SQLM_HIP_OK(hipMemcpyAsync(oh + o_fx, od + o_fx, (size_t)kf * 12, hipMemcpyDeviceToHost, c->stream));
     SQLM_HIP_OK(hipMemcpyAsync(oh + o_fn, od + o_fn, (size_t)kf * 12, hipMemcpyDeviceToHost, c->stream));
@@ -395,12 +236,172 @@ int sqlm_lidar_features(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, cons
     SQLM_HIP_OK(hipMemcpyAsync(oh + o_rc, od + o_rc, (size_t)kl * 8, hipMemcpyDeviceToHost, c->stream));
   }
   SQLM_HIP_OK(hipStreamSynchronize(c->stream));
-  std::memcpy(flat_xyz, oh + o_fx, (size_t)kf * 12);
-  std::memcpy(flat_normal, oh + o_fn, (size_t)kf * 12);
-  std::memcpy(less_xyz, oh + o_lx, (size_t)kl * 12);
-  std::memcpy(less_normal, oh + o_ln, (size_t)kl * 12);
-  std::memcpy(less_row_col, oh + o_rc, (size_t)kl * 8);
+  if (kf) {
+    std::memcpy(flat_xyz, oh + o_fx, (size_t)kf * 12);
+    std::memcpy(flat_normal, oh + o_fn, (size_t)kf * 12);
+  }
+  if (kl) {
+    std::memcpy(less_xyz, oh + o_lx, (size_t)kl * 12);
+    std::memcpy(less_normal, oh + o_ln, (size_t)kl * 12);
+    std::memcpy(less_row_col, oh + o_rc, (size_t)kl * 8);
+  }
+  if (ks) std::memcpy(co.sharp_xyz, oh + o_csx, (size_t)ks * 12);
+  if (kc) {
+    std::memcpy(co.less_xyz, oh + o_clx, (size_t)kc * 12);
+    std::memcpy(co.less_label, oh + o_clab, (size_t)kc * 4);
+    std::memcpy(co.less_rc, oh + o_crc, (size_t)kc * 8);
+  }
+  s->n_sharp = ks;
+  s->n_less_sharp = kc;
   s->have = true;
+  s->have_corner = lc != nullptr;
+  return SQLM_OK;
+}
+
+}  // namespace
+
+}  // namespace sqlm
+
+using namespace sqlm;
+
+extern "C" {
+
+int sqlm_lidar_features_host(int n_sweep, const int64_t *sweep_off, const float *xyz,
+                             const sqlm_lidar_feat_params *params, const double *extrinsic, int64_t *flat_off,
+                             float *flat_xyz, float *flat_normal, int64_t *less_off, float *less_xyz,
+                             float *less_normal, int32_t *less_row_col, sqlm_lidar_feat_state *state) {
+  LfParams p;
+  const void *outs[7] = {flat_off, less_off, flat_xyz, flat_normal, less_xyz, less_normal, less_row_col};
+  if (int r = lf_check(n_sweep, sweep_off, xyz, params, outs, 7, &p)) return r;
+  return lf_host(n_sweep, sweep_off, xyz, p, extrinsic, true, flat_off, flat_xyz, flat_normal, less_off, less_xyz,
+                 less_normal, less_row_col, state, nullptr, LcOut(), nullptr);
+}
+
+int sqlm_lidar_features(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, const float *xyz,
+                        const sqlm_lidar_feat_params *params, const double *extrinsic, int64_t *flat_off,
+                        float *flat_xyz, float *flat_normal, int64_t *less_off, float *less_xyz, float *less_normal,
+                        int32_t *less_row_col) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  LfParams p;
+  const void *outs[7] = {flat_off, less_off, flat_xyz, flat_normal, less_xyz, less_normal, less_row_col};
+  if (int r = lf_check(n_sweep, sweep_off, xyz, params, outs, 7, &p)) return r;
+  return lf_run(c, n_sweep, sweep_off, xyz, p, extrinsic, true, flat_off, flat_xyz, flat_normal, less_off, less_xyz,
+                less_normal, less_row_col, nullptr, LcOut());
+}
+
+// The checks sqlm_lidar_features_all and its host twin share
+static int lf_check_all(int n_sweep, const int64_t *sweep_off, const float *xyz, const sqlm_lidar_feat_params *params,
+                        const sqlm_lidar_corner_params *corner, const void *const *fouts, const LcOut &co, LfParams *p,
+                        LcParams *q, bool *do_flat) {
+  *do_flat = false;
+  for (int k = 0; k < 7; ++k) *do_flat = *do_flat || fouts[k];
+  if (int r = lf_check(n_sweep, sweep_off, xyz, params, fouts, *do_flat ? 7 : 0, p, true)) return r;
+  if (corner) {
+    const void *couts[6] = {co.sharp_off, co.sharp_xyz, co.less_off, co.less_xyz, co.less_label, co.less_rc};
+    if (int r = lc_check(sweep_off[n_sweep], params, corner, couts, 6, q)) return r;
+  }
+  return SQLM_OK;
+}
+
+int sqlm_lidar_features_all_host(int n_sweep, const int64_t *sweep_off, const float *xyz,
+                                 const sqlm_lidar_feat_params *params, const sqlm_lidar_corner_params *corner,
+                                 const double *extrinsic, int64_t *flat_off, float *flat_xyz, float *flat_normal,
+                                 int64_t *less_off, float *less_xyz, float *less_normal, int32_t *less_row_col,
+                                 int64_t *sharp_off, float *sharp_xyz, int64_t *less_sharp_off, float *less_sharp_xyz,
+                                 int32_t *less_sharp_label, int32_t *less_sharp_row_col,
+                                 sqlm_lidar_feat_state *flat_state, sqlm_lidar_corner_state *corner_state) {
+  LfParams p;
+  LcParams q;
+  bool do_flat;
+  const void *outs[7] = {flat_off, less_off, flat_xyz, flat_normal, less_xyz, less_normal, less_row_col};
+  const LcOut co{sharp_off, less_sharp_off, sharp_xyz, less_sharp_xyz, less_sharp_label, less_sharp_row_col};
+  if (int r = lf_check_all(n_sweep, sweep_off, xyz, params, corner, outs, co, &p, &q, &do_flat)) return r;
+  return lf_host(n_sweep, sweep_off, xyz, p, extrinsic, do_flat, flat_off, flat_xyz, flat_normal, less_off, less_xyz,
+                 less_normal, less_row_col, flat_state, corner ? &q : nullptr, co, corner ? corner_state : nullptr);
+}
+
+int sqlm_lidar_features_all(sqlm_ctx *c, int n_sweep, const int64_t *sweep_off, const float *xyz,
+                            const sqlm_lidar_feat_params *params, const sqlm_lidar_corner_params *corner,
+                            const double *extrinsic, int64_t *flat_off, float *flat_xyz, float *flat_normal,
+                            int64_t *less_off, float *less_xyz, float *less_normal, int32_t *less_row_col,
+                            int64_t *sharp_off, float *sharp_xyz, int64_t *less_sharp_off, float *less_sharp_xyz,
+                            int32_t *less_sharp_label, int32_t *less_sharp_row_col) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  LfParams p;
+  LcParams q;
+  bool do_flat;
+  const void *outs[7] = {flat_off, less_off, flat_xyz, flat_normal, less_xyz, less_normal, less_row_col};
+  const LcOut co{sharp_off, less_sharp_off, sharp_xyz, less_sharp_xyz, less_sharp_label, less_sharp_row_col};
+  if (int r = lf_check_all(n_sweep, sweep_off, xyz, params, corner, outs, co, &p, &q, &do_flat)) return r;
+  return lf_run(c, n_sweep, sweep_off, xyz, p, extrinsic, do_flat, flat_off, flat_xyz, flat_normal, less_off, less_xyz,
+                less_normal, less_row_col, corner ? &q : nullptr, co);
+}
+
+int sqlm_lidar_features_all_get_state(sqlm_ctx *c, sqlm_lidar_feat_state *flat_state,
+                                      sqlm_lidar_corner_state *cs) {
+  if (!c) return SQLM_ERR_INVALID_ARG;
+  LidarFeatSolver *s = c->lidar_feat;
+  if (!s || !s->have) return SQLM_ERR_STATE;
+  if (cs && !s->have_corner) return SQLM_ERR_STATE;
+  if (flat_state)
+    if (int r = sqlm_lidar_features_get_state(c, flat_state)) return r;
+  if (!cs) return SQLM_OK;
+  LcDev &e = s->lc;
+  const LfDev &d = e.f;
+  const size_t cells = (size_t)d.n_rows * d.p.col_num;
+  std::vector<int32_t> scan_n((size_t)d.n_rows, 0), cstate(cells, -3), sorted(cells, -1);
+  std::vector<uint8_t> mask(cells, 0), reason(cells, 0), edge(cells, 0);
+  std::vector<float> curv(cells, 0.f), angle;
+  if (cs->angle) angle.assign(cells * kLcOffsets, lc_quiet_nan());
+  if (d.n > 0) {
+    if (hipSetDevice(c->device) != hipSuccess) return SQLM_ERR_HIP;
+    SQLM_HIP_OK(hipStreamSynchronize(c->stream));
+    SQLM_HIP_OK(hipMemcpy(scan_n.data(), d.scan_n, (size_t)d.n_rows * 4, hipMemcpyDeviceToHost));
+    SQLM_HIP_OK(hipMemcpy(cstate.data(), e.state, cells * 4, hipMemcpyDeviceToHost));
+    SQLM_HIP_OK(hipMemcpy(sorted.data(), e.sorted, cells * 4, hipMemcpyDeviceToHost));
+    SQLM_HIP_OK(hipMemcpy(mask.data(), e.mask, cells, hipMemcpyDeviceToHost));
+    SQLM_HIP_OK(hipMemcpy(reason.data(), e.reason, cells, hipMemcpyDeviceToHost));
+    SQLM_HIP_OK(hipMemcpy(edge.data(), e.edge, cells, hipMemcpyDeviceToHost));
+    SQLM_HIP_OK(hipMemcpy(curv.data(), e.curv, cells * 4, hipMemcpyDeviceToHost));
+    for (int q = 0; q < d.n_rows; ++q)
+      if (scan_n[q] < 0 || scan_n[q] > d.p.col_num) return SQLM_ERR_HIP;
+    if (cs->angle) {  // the edge kernel once more, this time storing its angles
+      float *dev = nullptr;
+      if (hipMalloc((void **)&dev, angle.size() * sizeof(float)) != hipSuccess) return SQLM_ERR_OOM;
+      LcDev a = e;
+      a.angle = dev;
+      launch_lidar_corner_angles(a, c->stream);
+      hipError_t err = hipGetLastError();
+      if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
+      if (err == hipSuccess) err = hipMemcpy(angle.data(), dev, angle.size() * sizeof(float), hipMemcpyDeviceToHost);
+      (void)hipFree(dev);
+      if (err != hipSuccess) return SQLM_ERR_HIP;
+    }
+  }
+  lc_pack_state(d.p, d.n_rows, scan_n.data(), cstate.data(), mask.data(), curv.data(), sorted.data(), reason.data(),
+                edge.data(), angle.empty() ? nullptr : angle.data(), cs);
+  return SQLM_OK;
+}
+
+int sqlm_lidar_features_all_info(const sqlm_ctx *c, int32_t out[8]) {
+  if (!out) return SQLM_ERR_INVALID_ARG;
+  const LidarFeatSolver *s = c ? c->lidar_feat : nullptr;
+  out[0] = s ? s->launches : 0;
+  for (int k = 0; k < 5; ++k) out[1 + k] = s ? s->cstats[k] : 0;
+  out[6] = s ? (int32_t)s->n_less_sharp : 0;
+  out[7] = s ? (int32_t)s->n_sharp : 0;
+  return SQLM_OK;
+}
+
+int sqlm_lidar_corner_trig_probe(int64_t n, int which, const double *x, double *out) {
+  if (n < 0 || which < 0 || which > 2 || (n > 0 && (!x || !out))) return SQLM_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n; ++i) out[i] = which == 0 ? sqlm_acos(x[i]) : (which == 1 ? sqlm_sin(x[i]) : sqlm_cos(x[i]));
+  return SQLM_OK;
+}
+
+int sqlm_lidar_corner_angle_probe(int64_t n, const float *p1, const float *p2, float *out) {
+  if (n < 0 || (n > 0 && (!p1 || !p2 || !out))) return SQLM_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n; ++i) out[i] = lc_angle(p1 + 3 * i, p2 + 3 * i);
   return SQLM_OK;
 }
 

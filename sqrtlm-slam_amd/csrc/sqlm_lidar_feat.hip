@@ -28,7 +28,7 @@
 // does not depend on the order of arrival, so nothing depends on the batch or on
 // the launch geometry. No workgroup waits on another; every loop is bounded by
 // sizes the host checked. All stores are plain vector stores.
-#include "lidar_feat_dev.h"
+#include "lidar_corner_dev.h"
 #include "sqlm_internal.h"
 
 #pragma clang fp contract(off)
@@ -98,31 +98,6 @@ __global__ void __launch_bounds__(kLfBlock) k_lf_claim(LfDev d) {
   const unsigned long long key = ((unsigned long long)lf_bits(lf_dist(d.xyz + 3 * i)) << 32) | local;
   atomicMin(d.cell_key + cell, key);
   atomicMin(d.cell_first + cell, local);
-}
-
-// ascending bitonic sort of key[0 .. npow) by the whole workgroup; npow a power of two
-__device__ __forceinline__ void lf_sort(unsigned long long *key, int npow) {
-  for (int k = 2; k <= npow; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < npow; i += kLfBlock) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned long long a = key[i], b = key[l];
-          if ((a > b) == ((i & k) == 0)) {
-            key[i] = b;
-            key[l] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-__device__ __forceinline__ int lf_pow2(int n) {
-  int p = 2;
-  while (p < n) p <<= 1;
-  return p;
 }
 
 __global__ void __launch_bounds__(kLfBlock) k_lf_row(LfDev d) {
@@ -308,16 +283,6 @@ __global__ void __launch_bounds__(kLfBlock) k_lf_offsets(LfDev d) {
   }
 }
 
-__device__ __forceinline__ void lf_put(const LfDev &d, const float *p, float *out) {
-  if (d.has_ext) {
-    lf_transform(d.ext, p, out);
-  } else {
-    out[0] = p[0];
-    out[1] = p[1];
-    out[2] = p[2];
-  }
-}
-
 __global__ void __launch_bounds__(64) k_lf_emit(LfDev d) {
   const int g = blockIdx.x;
   if (g >= d.n_rows * d.p.n_sub || d.region_cnt[g] == 0) return;
@@ -347,17 +312,21 @@ __global__ void __launch_bounds__(64) k_lf_emit(LfDev d) {
 
 }  // namespace
 
-int launch_lidar_feat(const LfDev &d, hipStream_t st) {
+int launch_lidar_feat_image(const LfDev &d, hipStream_t st) {
   const unsigned pts = (unsigned)((d.n + kLfBlock - 1) / kLfBlock);
-  const unsigned regions = (unsigned)(d.n_rows * d.p.n_sub);
   hipLaunchKernelGGL(k_lf_point, dim3(pts), dim3(kLfBlock), 0, st, d);
   hipLaunchKernelGGL(k_lf_half, dim3(pts), dim3(kLfBlock), 0, st, d);
   hipLaunchKernelGGL(k_lf_claim, dim3(pts), dim3(kLfBlock), 0, st, d);
   hipLaunchKernelGGL(k_lf_row, dim3((unsigned)d.n_rows), dim3(kLfBlock), 0, st, d);
+  return 4;
+}
+
+int launch_lidar_feat_flat(const LfDev &d, hipStream_t st) {
+  const unsigned regions = (unsigned)(d.n_rows * d.p.n_sub);
   hipLaunchKernelGGL(k_lf_region, dim3(regions), dim3(kLfBlock), 0, st, d);
   hipLaunchKernelGGL(k_lf_offsets, dim3(1), dim3(kLfBlock), 0, st, d);
   hipLaunchKernelGGL(k_lf_emit, dim3(regions), dim3(64), 0, st, d);
-  return 7;
+  return 3;
 }
 
 }  // namespace sqlm

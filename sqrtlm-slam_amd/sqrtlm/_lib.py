@@ -61,6 +61,9 @@ EXPORTS = [
     # LiDAR flat-feature extraction (Frame::lidarProcess, flat-point path) and its host twin
     "sqlm_lidar_features", "sqlm_lidar_features_host", "sqlm_lidar_features_get_state", "sqlm_lidar_features_info",
     "sqlm_lidar_feat_trig_probe",
+    # both branches of Frame::ExtractFeaturePoints on one range image (the corner branch, Frame.cc:861-1038)
+    "sqlm_lidar_features_all", "sqlm_lidar_features_all_host", "sqlm_lidar_features_all_get_state",
+    "sqlm_lidar_features_all_info", "sqlm_lidar_corner_trig_probe", "sqlm_lidar_corner_angle_probe",
     # LiDAR depth image and keypoint depth association (Frame.cc:290-313, :333-408) and its host twin
     "sqlm_lidar_depth", "sqlm_lidar_depth_host", "sqlm_lidar_depth_get_state", "sqlm_lidar_depth_info",
 ]
@@ -230,6 +233,15 @@ def lib() -> C.CDLL:
             L.sqlm_lidar_features_get_state.argtypes = [P, P]
             L.sqlm_lidar_features_info.argtypes = [P, P]
             L.sqlm_lidar_feat_trig_probe.argtypes = [C.c_int64, P, P, P]
+        if hasattr(L, "sqlm_lidar_features_all"):
+            P = C.c_void_p
+            # ctx, n_sweep, sweep_off, xyz, params, corner, extrinsic, 7 flat outputs, 6 corner outputs
+            L.sqlm_lidar_features_all.argtypes = [P, C.c_int] + [P] * 18
+            L.sqlm_lidar_features_all_host.argtypes = [C.c_int] + [P] * 20
+            L.sqlm_lidar_features_all_get_state.argtypes = [P, P, P]
+            L.sqlm_lidar_features_all_info.argtypes = [P, P]
+            L.sqlm_lidar_corner_trig_probe.argtypes = [C.c_int64, C.c_int, P, P]
+            L.sqlm_lidar_corner_angle_probe.argtypes = [C.c_int64, P, P, P]
         if hasattr(L, "sqlm_lidar_depth"):
             P = C.c_void_p
             # [ctx,] n_frame, sweep_off, xyz, key_off, key_xy, key_un_xy, rows, cols, intrinsic, extrinsic, cam,
@@ -269,6 +281,17 @@ class LidarFeatState(C.Structure):
     """sqlm_lidar_feat_state: caller-allocated arrays, any may be NULL."""
     _fields_ = [(k, C.c_void_p) for k in ("ring", "scan_off", "scan_src", "scan_col", "image_index", "mask",
                                           "curvature", "neighbours", "sorted", "reason")]
+
+
+class LidarCornerParams(C.Structure):
+    """sqlm_lidar_corner_params."""
+    _fields_ = [("max_corner_sharp", C.c_int32), ("max_corner_less_sharp", C.c_int32), ("sharp_curv_th", C.c_double),
+                ("ground_z_bound", C.c_double), ("corner_ring_enabled", C.c_uint8 * LF_MAX_ROWS)]
+
+
+class LidarCornerState(C.Structure):
+    """sqlm_lidar_corner_state: caller-allocated arrays, any may be NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("cell_state", "mask", "curvature", "sorted", "reason", "edge", "angle")]
 
 
 def check(status: int, what: str) -> None:

@@ -6,7 +6,13 @@ reference's ``Frame::lidarProcess`` (sqlm_lidar_features, include/sqrtlm.h).
 ``features_host`` the same text on the CPU; ``lidarProcess`` mirrors the
 reference interface for one frame; ``make_sweep`` generates a seeded synthetic
 sweep; ``set_lidar_edges`` hands the less-flat clouds of several sweeps to the
-existing cloud path of local BA pass 3."""
+existing cloud path of local BA pass 3.
+
+``CornerParams`` adds the settings of the corner branch; ``features_all`` /
+``features_all_host`` run both branches on one range image
+(sqlm_lidar_features_all), ``features_all_state`` / ``features_all_info`` read
+back what the last call did, and ``set_lidar_edge_sets`` hands the less-flat and
+the less-sharp clouds to local BA pass 3 as a flat and a corner set."""
 from __future__ import annotations
 
 import ctypes as C
@@ -67,6 +73,43 @@ class Params:
             setattr(p, k, int(getattr(self, k)))
         p.surf_curv_th, p.max_sq_dis, p.deg_diff = float(self.surf_curv_th), float(self.max_sq_dis), float(self.deg_diff)
         p.ring_enabled[:] = self.enabled().tolist()
+        return p
+
+
+CORNER_REASONS = {0: "none", 1: "ground", 2: "masked", 3: "curvature", 4: "unstable", 5: "over_cap", 6: "picked"}
+LC_NONE, LC_GROUND, LC_MASKED, LC_CURVATURE, LC_UNSTABLE, LC_OVER_CAP, LC_PICKED = range(7)
+# the six distinct (row, column) offsets of Frame.cc:929-938, bit k of a cell's edge mask
+CORNER_OFFSETS = ((-1, 0), (1, 0), (0, -1), (0, 1), (-1, -1), (1, -1))
+
+
+@dataclass
+class CornerParams:
+    """The corner settings of lidarConfig with the defaults cfg/lidar_slam.yaml
+    ships. The ring range is the reference's: ring i (0-based) takes part when
+    lower <= i + 1 and i < upper."""
+    max_corner_sharp: int = 3
+    max_corner_less_sharp: int = 30
+    sharp_curv_th: float = 20.0
+    ground_z_bound: float = -1.5
+    lower_ring_num_sharp_point: int = 1
+    upper_ring_num_sharp_point: int = 40
+    ring_enabled: np.ndarray | None = field(default=None, repr=False)  # overrides the range
+
+    def enabled(self) -> np.ndarray:
+        """corner_ring_enabled[128] from the two bounds of Frame.cc:862."""
+        if self.ring_enabled is not None:
+            e = np.zeros(_lib.LF_MAX_ROWS, np.uint8)
+            src = np.asarray(self.ring_enabled, np.uint8)
+            e[:len(src)] = src
+            return e
+        i = np.arange(_lib.LF_MAX_ROWS)
+        return ((self.lower_ring_num_sharp_point <= i + 1) & (i < self.upper_ring_num_sharp_point)).astype(np.uint8)
+
+    def as_c(self) -> _lib.LidarCornerParams:
+        p = _lib.LidarCornerParams()
+        p.max_corner_sharp, p.max_corner_less_sharp = int(self.max_corner_sharp), int(self.max_corner_less_sharp)
+        p.sharp_curv_th, p.ground_z_bound = float(self.sharp_curv_th), float(self.ground_z_bound)
+        p.corner_ring_enabled[:] = self.enabled().tolist()
         return p
 
 
@@ -161,6 +204,138 @@ def features_state(ctx) -> dict:
     return _trim_state(a, n_sweep, n, params)
 
 
+def _corner_outputs(n_sweep, n):
+    m = max(n, 1)
+    return dict(sharp_off=np.zeros(n_sweep + 1, np.int64), sharp_xyz=np.zeros((m, 3), np.float32),
+                less_sharp_off=np.zeros(n_sweep + 1, np.int64), less_sharp_xyz=np.zeros((m, 3), np.float32),
+                less_sharp_label=np.zeros(m, np.int32), less_sharp_rc=np.zeros((m, 2), np.int32))
+
+
+_CORNER_ORDER = ("sharp_off", "sharp_xyz", "less_sharp_off", "less_sharp_xyz", "less_sharp_label", "less_sharp_rc")
+_FLAT_ORDER = ("flat_off", "flat_xyz", "flat_normal", "less_off", "less_xyz", "less_normal", "less_rc")
+
+
+def _trim_corner(o):
+    ks, kl = int(o["sharp_off"][-1]), int(o["less_sharp_off"][-1])
+    o["sharp_xyz"] = o["sharp_xyz"][:ks].copy()
+    for k in ("less_sharp_xyz", "less_sharp_label", "less_sharp_rc"):
+        o[k] = o[k][:kl].copy()
+    return o
+
+
+def _corner_state_arrays(n_sweep, n, p: Params):
+    m, S = max(n, 1), max(n_sweep * p.row_num, 1)
+    a = dict(cell_state=np.zeros((S, p.col_num), np.int32), mask=np.zeros(m, np.uint8), curvature=np.zeros(m, np.float32),
+             sorted=np.zeros(m, np.int32), reason=np.zeros(m, np.uint8), edge=np.zeros((S, p.col_num), np.uint8),
+             angle=np.zeros((S, p.col_num, 6), np.float32))
+    st = _lib.LidarCornerState()
+    for k, v in a.items():
+        setattr(st, k, v.ctypes.data)
+    return a, st
+
+
+def _trim_corner_state(a, n_sweep, ns, p: Params):
+    S = n_sweep * p.row_num
+    for k in ("cell_state", "edge", "angle"):
+        a[k] = a[k][:S].copy()
+    for k in ("mask", "curvature", "sorted", "reason"):
+        a[k] = a[k][:ns].copy()
+    return a
+
+
+def _all_args(sweeps, params, corner, extrinsic, flat):
+    off, xyz = _pack(sweeps)
+    n_sweep, n = len(off) - 1, int(off[-1])
+    o = _outputs(n_sweep, n) if flat else {}
+    if corner is not None:
+        o.update(_corner_outputs(n_sweep, n))
+    pc, cc, e = params.as_c(), None if corner is None else corner.as_c(), _ext(extrinsic)
+    args = [n_sweep, ptr(off), ptr(xyz), C.addressof(pc), None if cc is None else C.addressof(cc), ptr(e)]
+    args += [ptr(o[k]) if flat else None for k in _FLAT_ORDER]
+    args += [ptr(o[k]) if corner is not None else None for k in _CORNER_ORDER]
+    return off, n_sweep, n, o, args, (pc, cc, e, xyz)
+
+
+def _finish_all(o, flat, corner):
+    if flat:
+        o = _trim(o)
+    if corner is not None:
+        o = _trim_corner(o)
+    return o
+
+
+def features_all_host(sweeps, params: Params, corner: CornerParams | None = None, extrinsic=None, state: bool = False,
+                      flat: bool = True) -> dict:
+    """sqlm_lidar_features_all_host: the flat outputs of ``features_host``
+    (unless ``flat`` is False) and, with ``corner``, sharp_off, sharp_xyz,
+    less_sharp_off, less_sharp_xyz, less_sharp_label, less_sharp_rc; with
+    ``state`` the flat state under "state" and the corner state under
+    "corner_state"."""
+    off, n_sweep, n, o, args, keep = _all_args(sweeps, params, corner, extrinsic, flat)
+    a, st = _state_arrays(n_sweep, n, params) if state else (None, None)
+    ca, cst = _corner_state_arrays(n_sweep, n, params) if state and corner is not None else (None, None)
+    check(lib().sqlm_lidar_features_all_host(*args, C.addressof(st) if st is not None else None,
+                                             C.addressof(cst) if cst is not None else None),
+          "sqlm_lidar_features_all_host")
+    o = _finish_all(o, flat, corner)
+    if state:
+        o["state"] = _trim_state(a, n_sweep, n, params)
+        if ca is not None:
+            o["corner_state"] = _trim_corner_state(ca, n_sweep, len(o["state"]["mask"]), params)
+    return o
+
+
+def features_all(ctx, sweeps, params: Params, corner: CornerParams | None = None, extrinsic=None,
+                 flat: bool = True) -> dict:
+    """sqlm_lidar_features_all: both branches of every sweep of the batch on
+    one upload and one range image. ``corner`` None runs the flat branch alone
+    and equals ``features``."""
+    off, n_sweep, n, o, args, keep = _all_args(sweeps, params, corner, extrinsic, flat)
+    check(lib().sqlm_lidar_features_all(ctx._h, *args), "sqlm_lidar_features_all")
+    ctx._lidar_feat_shape = (n_sweep, n, params)
+    ctx._lidar_corner = corner is not None
+    return _finish_all(o, flat, corner)
+
+
+def features_all_state(ctx) -> dict:
+    """{"state": flat state, "corner_state": corner state} of the context's
+    last ``features_all`` (the corner state only if it ran a corner stage)."""
+    n_sweep, n, params = ctx._lidar_feat_shape
+    a, st = _state_arrays(n_sweep, n, params)
+    ca, cst = _corner_state_arrays(n_sweep, n, params) if ctx._lidar_corner else (None, None)
+    check(lib().sqlm_lidar_features_all_get_state(ctx._h, C.addressof(st), C.addressof(cst) if cst is not None else None),
+          "sqlm_lidar_features_all_get_state")
+    out = dict(state=_trim_state(a, n_sweep, n, params))
+    if ca is not None:
+        out["corner_state"] = _trim_corner_state(ca, n_sweep, len(out["state"]["mask"]), params)
+    return out
+
+
+def features_all_info(ctx=None) -> dict:
+    out = (C.c_int32 * 8)()
+    check(lib().sqlm_lidar_features_all_info(ctx._h if ctx is not None else None, out), "sqlm_lidar_features_all_info")
+    return dict(launches=out[0], seeds_grown=out[1], cells_labelled=out[2], cells_unstable=out[3],
+                largest_segment=out[4], most_levels=out[5], less_sharp=out[6], sharp=out[7])
+
+
+def corner_trig_probe(which: str, x) -> np.ndarray:
+    """sqlm_acos / sqlm_sin / sqlm_cos as the library compiled them."""
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.zeros_like(x)
+    check(lib().sqlm_lidar_corner_trig_probe(x.size, {"acos": 0, "sin": 1, "cos": 2}[which], ptr(x), ptr(out)),
+          "sqlm_lidar_corner_trig_probe")
+    return out
+
+
+def corner_angle_probe(p1, p2) -> np.ndarray:
+    """The float angle of the corner branch's edge predicate for point pairs, on the host."""
+    p1 = np.ascontiguousarray(p1, np.float32).reshape(-1, 3)
+    p2 = np.ascontiguousarray(p2, np.float32).reshape(-1, 3)
+    out = np.zeros(len(p1), np.float32)
+    check(lib().sqlm_lidar_corner_angle_probe(len(p1), ptr(p1), ptr(p2), ptr(out)), "sqlm_lidar_corner_angle_probe")
+    return out
+
+
 def features_info(ctx=None) -> dict:
     out = (C.c_int32 * 8)()
     check(lib().sqlm_lidar_features_info(ctx._h if ctx is not None else None, out), "sqlm_lidar_features_info")
@@ -177,13 +352,19 @@ def trig_probe(y, x=None) -> np.ndarray:
     return out
 
 
-def lidarProcess(ctx, cloud, params: Params, extrinsic=None):
+def lidarProcess(ctx, cloud, params: Params, extrinsic=None, corner: CornerParams | None = None):
     """One frame as the reference's Frame constructor leaves it: returns
     (surface_points_flat, surface_points_less_flat,
     surface_points_less_flat_normal, surface_points_less_flat_index), the
-    clouds in the extrinsic's target frame."""
-    o = features(ctx, [cloud], params, extrinsic)
-    return o["flat_xyz"], o["less_xyz"], o["less_normal"], o["less_rc"]
+    clouds in the extrinsic's target frame. With ``corner`` both branches run
+    (``features_all``) and the tuple continues with (corner_points_sharp,
+    corner_points_less_sharp, the less-sharp labels)."""
+    if corner is None:
+        o = features(ctx, [cloud], params, extrinsic)
+        return o["flat_xyz"], o["less_xyz"], o["less_normal"], o["less_rc"]
+    o = features_all(ctx, [cloud], params, corner, extrinsic)
+    return (o["flat_xyz"], o["less_xyz"], o["less_normal"], o["less_rc"], o["sharp_xyz"], o["less_sharp_xyz"],
+            o["less_sharp_label"])
 
 
 def set_lidar_edges(ctx, pose_index: int, feats: dict, Twc, query: int, info: float, dist_sq_threshold: float) -> int:
@@ -199,6 +380,27 @@ def set_lidar_edges(ctx, pose_index: int, feats: dict, Twc, query: int, info: fl
                                      Twc[query], feats["less_normal"][lo:hi], info, dist_sq_threshold)
 
 
+def set_lidar_edge_sets(ctx, pose_index: int, feats: dict, Twc, query: int, info: float, dist_sq_threshold: float,
+                        corner_info: float | None = None, corner_dist_sq_threshold: float | None = None) -> list:
+    """Local BA pass 3 from a ``features_all`` result: a flat set (sweep
+    ``query``'s less-flat points and normals against every other sweep's
+    less-flat cloud) and a corner set (its less-sharp points against the other
+    sweeps' less-sharp clouds) through Context.set_lidar_from_cloud_sets;
+    returns the pair count of each."""
+    others = [k for k in range(len(feats["less_off"]) - 1) if k != query]
+    sets = []
+    for kind, off, xyz, nrm, w, th in (
+            (0, feats["less_off"], feats["less_xyz"], feats["less_normal"], info, dist_sq_threshold),
+            (1, feats["less_sharp_off"], feats["less_sharp_xyz"], None,
+             info if corner_info is None else corner_info,
+             dist_sq_threshold if corner_dist_sq_threshold is None else corner_dist_sq_threshold)):
+        lo, hi = int(off[query]), int(off[query + 1])
+        sets.append(dict(kind=kind, map_clouds=[xyz[off[k]:off[k + 1]] for k in others], map_Twc=[Twc[k] for k in others],
+                         query_xyz=xyz[lo:hi], query_Twc=Twc[query], query_normal=None if nrm is None else nrm[lo:hi],
+                         info=w, dist_sq_threshold=th))
+    return ctx.set_lidar_from_cloud_sets(pose_index, sets)
+
+
 def ring_elevation_deg(ring):
     """The elevation at the centre of a virtual ring (CalculateRingAndTime inverted)."""
     ring = np.asarray(ring, np.float64)
@@ -207,13 +409,15 @@ def ring_elevation_deg(ring):
 
 def make_sweep(seed: int, n_az: int = 1800, order: str = "ring", noise: float = 0.01, dropout: float = 0.02,
                start_deg: float = 0.0, n_boxes: int = 6, room: float = 25.0, ground_z: float = -1.73,
-               max_range: float = 80.0, pose=None, rings=None) -> np.ndarray:
+               max_range: float = 80.0, pose=None, rings=None, n_poles: int = 0) -> np.ndarray:
     """A seeded synthetic sweep: a ground plane, four vertical walls and
     ``n_boxes`` boxes, sampled along 64 elevation rays x ``n_az`` azimuths
     (clockwise, as the sensor turns), with range noise and dropouts. ``order``
     is "ring" (ring-major) or "azimuth" (azimuth-major input order). ``pose``
     (R, t) places the sensor in the scene; the points are in the sensor frame. ``rings`` restricts the rays to those
-    virtual rings (all 64 by default)."""
+    virtual rings (all 64 by default). ``n_poles`` adds that many thin free-standing
+    poles (0.3 m square, 6 m tall), the scenery that yields corner points; the
+    default of 0 leaves every existing seed's sweep as it was."""
     rng = np.random.default_rng(seed)
     rings = np.arange(N_SCANS) if rings is None else np.asarray(list(rings), np.int64)
     n_el = len(rings)
@@ -232,6 +436,11 @@ def make_sweep(seed: int, n_az: int = 1800, order: str = "ring", noise: float = 
             c[:2] += 6.0
         h = np.array([brng.uniform(0.8, 3.0), brng.uniform(0.8, 3.0), brng.uniform(1.0, 4.0)])
         boxes.append((c - [h[0], h[1], 0.0], c + [h[0], h[1], h[2]], False))
+    prng = np.random.default_rng([2000 + n_poles, seed])  # the poles move with the sweep's seed; the boxes above do not
+    for _ in range(n_poles):
+        a, rad = prng.uniform(0.0, 2.0 * np.pi), prng.uniform(5.0, room - 6.0)
+        c = np.array([rad * np.cos(a), rad * np.sin(a), ground_z])
+        boxes.append((c - [0.15, 0.15, 0.0], c + [0.15, 0.15, 6.0], False))
     best = np.full(len(dw), np.inf)
     with np.errstate(divide="ignore", invalid="ignore"):
         inv = 1.0 / dw
